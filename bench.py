@@ -7,7 +7,10 @@ random playouts (arena semantics: pass when stuck, game over when nobody can mov
 GameResult scoring) from 256 synthetic mid-game positions (20 random plies from the
 empty board), all resident in HBM before the timed region.  The line's `value` is the
 reference as shipped: its default frontier move order (BLOKUS_USE_FRONTIER_MOVEGEN=1,
-engine/move_generator.py:66, :148; kernel k_rollout_fr).  The default line also carries:
+engine/move_generator.py:66, :148; kernel k_rollout_fr).  A plain run sets up, warms up,
+times the steps and prints that line (value, ms_per_step, roofline); `--dump-outputs DIR`
+also writes the last timed step's result records to DIR/<field>.npy.  With `--full` each
+line also carries its cpu_baseline (one GPU), and the default line also carries:
   naive_order  the same measurement in naive order (BLOKUS_USE_FRONTIER_MOVEGEN=0, k_rollout)
   config5      BASELINE configs[4]: 65,536 MCTSAgent searches x 4,096 iterations (one
                launch after a 64-iteration warmup), strong scaling over the ranks
@@ -72,6 +75,14 @@ def parse(argv=None):
                          "run directly with N > 1, bench.py starts the N rank processes itself")
     ap.add_argument("--selftest", action="store_true",
                     help="CPU check of the N-rank path (gloo): launch, shard, gather, compare with one process")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the CPU baselines and, for config3, the "
+                         "other move order and the config5 / config4 objects (each still has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's share) to "
+                         "DIR/<name>.npy as float32 / float64 arrays, at most 64 MB in all (beyond that a fixed, "
+                         "seeded sample of the rows); same arguments, same inputs, so two builds compare output "
+                         "for output")
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 20; config5: 1)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default: 3; config5: 1, "
                                                               "a 64-iteration chunk)")
@@ -131,6 +142,8 @@ def parse(argv=None):
     ap.add_argument("--extra-config4-games", type=int, default=1024,
                     help="config3 line's config4 object: arena games per rank (weak scaling; 8 ranks = 8,192)")
     a = ap.parse_args(argv)
+    if not a.full:  # a plain run does only what its own value needs
+        a.no_cpu_baseline = a.no_second_order = a.no_extra_configs = True
     if a.steps is None:
         a.steps = 1 if a.workload in ("config5", "config4") else (200 if a.workload == "config2" else 20)
     if a.warmup is None:
@@ -383,6 +396,41 @@ def ranks_fields(dist, rank_elapsed, steps, check=None, sha=None):
     return out
 
 
+DUMP_BYTES_MAX = 64 * 10 ** 6  # every file's 128-byte header included
+
+
+def dump_outputs(args, arrays):
+    """--dump-outputs DIR: write `arrays` (name -> numpy array, one row per work item of the
+    last timed step, all of the same length; a structured array gives one file per field)
+    as DIR/<name>.npy.  Integers of up to 16 bits and float32 go out as float32, everything
+    else as float64 (exact for every 32-bit integer).  Past 64 MB in all, every file keeps
+    the same rows, a fixed sample drawn with --seed, and DIR/sample_rows.npy lists them."""
+    import numpy as np
+    if not args.dump_outputs:
+        return
+    flat = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        for f in a.dtype.names or (None,):
+            if f != "reserved":
+                flat[name if f is None else f"{name}_{f}" if name else f] = a if f is None else a[f]
+    conv = {k: (np.float32 if (a.dtype.kind == "f" and a.itemsize <= 4) or (a.dtype.kind in "biu" and a.itemsize <= 2)
+                else np.float64) for k, a in flat.items()}
+    n = len(next(iter(flat.values())))
+    assert all(len(a) == n for a in flat.values()), {k: a.shape for k, a in flat.items()}
+    row_bytes = sum(int(np.prod(a.shape[1:], dtype=np.int64)) * np.dtype(conv[k]).itemsize for k, a in flat.items())
+    keep = (DUMP_BYTES_MAX - 128 * (len(flat) + 1)) // (row_bytes + 8)
+    rows = None
+    if n > keep:
+        rows = np.sort(np.random.RandomState(args.seed % 2 ** 32).choice(n, keep, replace=False))
+        flat = {k: a[rows] for k, a in flat.items()}
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for k, a in flat.items():
+        np.save(os.path.join(args.dump_outputs, k + ".npy"), np.ascontiguousarray(a, dtype=conv[k]))
+    if rows is not None:
+        np.save(os.path.join(args.dump_outputs, "sample_rows.npy"), rows.astype(np.float64))
+
+
 def traffic_for(kernel, units_per_launch):
     """PMC HBM bytes and VALU instructions of ONE launch of `kernel` holding
     `units_per_launch` units of work (playouts, board-players or simulations), from the
@@ -588,6 +636,9 @@ def run_config3(args, world, rank, local, dist):
     extras = {} if args.no_extra_configs else run_extra_configs(args, world, rank, local, dist)
     if rank != 0:
         return None
+    if args.dump_outputs:  # the last timed step's result records (one per playout), field by field
+        from reinforcementlearning_blokus_amd import _native as N
+        dump_outputs(args, {"": m["out"].cpu().numpy().view(N.RESULT_DTYPE).reshape(-1)})
     f = _config3_fields(args, args.order, m, world)
     line = {
         "metric": METRIC, "value": f["value"], "unit": "sims/s", "n_gpus": world, "steps": args.steps,
@@ -637,7 +688,7 @@ def run_extra_configs(args, world, rank, local, dist):
                                                         rollout_policy="random")),
                          ("config4", run_config4, dict(games=args.extra_config4_games * world))):
         sub = copy.copy(args)
-        sub.__dict__.update(kw, steps=1, warmup=1, workload=name, check_gather=False)
+        sub.__dict__.update(kw, steps=1, warmup=1, workload=name, check_gather=False, dump_outputs=None)
         try:
             obj = fn(sub, world, rank, local, dist)
         except Exception as e:  # noqa: BLE001 -- reported in the line, never hidden
@@ -712,6 +763,7 @@ def run_config5(args, world, rank, local, dist):
         check = _config5_check_gather(args, gpu, batch, policy, mine, roots_all, sets_all, rank, world, dist)
     if rank != 0:
         return None
+    dump_outputs(args, {"": res})  # the last step's search records of this rank's games
     value = sims / elapsed
     kernel_ms = sum(kms)  # last step's launches (HIP events per chunk)
     # SURVEY 8(d) bytes: 256 B state read + write per rollout ply + 32 B result per
@@ -908,6 +960,13 @@ def run_config4(args, world, rank, local, dist):
                 f"{len(bad)} of {total} games differ ({len(got)} gathered; first {bad[:4]})"
     if rank != 0:
         return None
+    if args.dump_outputs:  # this rank's game records of the last step, by game index
+        import numpy as np
+        by = sorted(recs, key=lambda r: r["game_index"])
+        dump_outputs(args, {"game_index": np.array([r["game_index"] for r in by], dtype=np.int32),
+                            "final_scores": np.array([[r["final_scores"][str(p + 1)] for p in range(4)] for r in by],
+                                                     dtype=np.int32),
+                            "moves_made": np.array([r["moves_made"] for r in by], dtype=np.int32)})
     # roofline of the dominant kernel, the bk_mcts kernel with the most launch time
     # (k_mcts_coop_h at these batch sizes; bk_mcts picks it by searches per CU): SURVEY
     # 8(d) bytes, 256 B state read + write per rollout ply, plus 120 B per simulation
@@ -1072,6 +1131,9 @@ def run_config2(args, world, rank, local, dist):
     elapsed, (pairs,) = reduce_max_sum(dist, dev, elapsed, [n * args.steps])
     if rank != 0:
         return None
+    if args.dump_outputs:  # the masks as 32-bit words: exact in float64
+        dump_outputs(args, {"counts": cnt.cpu().numpy(),
+                            "mask_words": masks.cpu().numpy().view(np.uint32).reshape(n, N.N_ORIENTS, 14)})
     value = pairs / elapsed
     achieved = n * MOVEGEN_B / (kernel_ms * 1e-3) / 1e9
     traffic, valu_insts, tsrc = traffic_for(kname, n)

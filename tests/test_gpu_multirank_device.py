@@ -43,7 +43,7 @@ def _ranks_ok(rk, n_indices):
 
 def test_config3_two_ranks_equal_one_launch_of_their_games():
     d = _bench(["--workload", "config3", "--games", "16", "--rollouts", "64", "--steps", "2", "--warmup", "1",
-                "--no-extra-configs"])
+                "--full", "--no-extra-configs"])
     assert d["n_gpus"] == 2 and d["value"] > 0
     assert d["config"]["playouts_per_step"] == 16 * 64 and d["config"]["move_order"] == "frontier"
     assert d["gather_check"] == "ok"
@@ -54,10 +54,10 @@ def test_config3_two_ranks_equal_one_launch_of_their_games():
 
 
 def test_default_line_extra_configs_two_ranks():
-    """The default line's config5 / config4 objects at N = 2 (small sizes): each carries
+    """The `--full` line's config5 / config4 objects at N = 2 (small sizes): each carries
     its own value and the N-rank fields; no error recorded."""
     d = _bench(["--workload", "config3", "--games", "8", "--rollouts", "64", "--steps", "1", "--warmup", "1",
-                "--no-second-order", "--extra-config5-games", "66", "--extra-config5-iterations", "64",
+                "--full", "--no-second-order", "--extra-config5-games", "66", "--extra-config5-iterations", "64",
                 "--extra-config4-games", "6"], timeout=600)
     for name, n in (("config5", 66), ("config4", 12)):
         o = d[name]
