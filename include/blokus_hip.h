@@ -70,7 +70,10 @@ typedef struct bk_state {
 #define BK_SEM_ROLLOUT 1 /* A: MCTSAgent._rollout, mcts/mcts_agent.py:470-554 (cap, break, delta) */
 #define BK_SEM_ADVANCE 2 /* play max_plies random moves (pass when stuck, stop early when nobody
                             can move) and return the reached state: the batched analogue of
-                            tests/utils_game_states.py:12-57 generate_random_valid_state      */
+                            tests/utils_game_states.py:12-57 generate_random_valid_state.
+                            With the budget used, current_player is the seat after the last
+                            mover, whether or not it can move (nobody passes after the last
+                            placement); out_mask holds the seats found stuck on the way     */
 
 /* Legal-move list order used to turn a random index into a move */
 #define BK_ORDER_NAIVE 0    /* piece asc, orientation asc, anchor row-major:

@@ -1075,6 +1075,7 @@ def _run_games_device(run_config: RunConfig, idx: List[int], seats: List[Mapping
                             "mcts_games_per_job": tl["mcts_job_games"] / max(1, tl["mcts_jobs"]),
                             "job_plies_max_over_mean": tl["job_plies_max_over_mean"] / max(1, tl["mcts_jobs"]),
                             "handback": early,
+                            "handback_games": tl["handback_games"],
                             "handback_ms_mean": 1e3 * tl["handback_s"] / max(1, tl["handback_games"]),
                             "games_in_search_per_step": tl["search_games_per_step"] / max(1, prof["rounds"])}
         stream.synchronize()

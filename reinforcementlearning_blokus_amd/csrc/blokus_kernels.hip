@@ -2903,8 +2903,12 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a) {
                 start_game<FR>(a, g, slab, slot, next, htab);
             }
             if (arena) {
+                // (ADVANCE: once the placement budget is used nobody passes any more -- the
+                // player after the last mover is left to move, stuck or not:
+                // generate_random_valid_state leaves its loop before it looks at that player)
 #pragma unroll 1
-                for (int s = 0; s < 4 && ((g.out >> g.cur) & 1u) && g.out != 0xFu && (advance || g.turns < g.cap); ++s) {
+                for (int s = 0; s < 4 && ((g.out >> g.cur) & 1u) && g.out != 0xFu &&
+                                (advance ? g.plies : g.turns) < g.cap; ++s) {
                     g.passes++; g.turns++; g.since_move++;
                     g.cur = (g.cur + 1) & 3;
                 }
@@ -5914,7 +5918,8 @@ static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, 
     // SIMD -- pull the rest), the other waves finish and free their SIMD time.  57.0 M ->
     // 60.2 M playouts/s (profiles/r03/sweeps/handout.jsonl).  The frontier-order kernels
     // keep 0 (22.4 vs 21.5 M: their playout lengths vary more).  Results depend only on the
-    // playout id, not on the slot (tests/test_gpu_parity.py slot independence).
+    // playout id, not on the slot (tests/test_gpu_parity.py slot independence; the three
+    // hand-outs over several resident rounds: tests/test_gpu_handout.py).
     a.handout = (int)tune_or(h, BK_TUNE_HANDOUT, a.handout);
     if (a.handout < 0 || a.handout > 2) a.handout = 0;
     {

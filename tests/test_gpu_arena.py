@@ -153,6 +153,13 @@ def test_batched_cap_at_max_turns():
             assert got[k] == ref[k], (gi, k)
 
 
+def _assert_handback_ran(timeline):
+    """The hand-back cases mean nothing unless the runner took its per-search hand-back
+    path: the batch profile says so and counts the games handed back."""
+    assert timeline["handback"] is True, timeline
+    assert timeline["handback_games"] >= 1, timeline
+
+
 @pytest.mark.parametrize("coop,handback", [("1", False), ("0", False), ("1", True)])
 def test_batched_arena_matches_bench_strength_reference_records(coop, handback, monkeypatch):
     """bench.py's config-4 seats at full strength -- MCTS 64 iterations with 50-ply
@@ -161,11 +168,15 @@ def test_batched_arena_matches_bench_strength_reference_records(coop, handback, 
     20260301 (tests/golden/arena_bench.json, tools/gen_fixtures.py arena_bench), with the
     cooperative search kernel (the default at these batch sizes) and the per-lane one, and
     with per-search hand-back (ArenaOptions.handback)."""
+    from reinforcementlearning_blokus_amd.arena import runner
     from reinforcementlearning_blokus_amd.arena.runner import run_games_batched
     monkeypatch.setenv("BK_MCTS_COOP", coop)
+    monkeypatch.delenv("BK_ARENA_CAPTURE", raising=False)  # a capture directory turns hand-back off
     fx = load_golden("arena_bench.json")
     cfg = RunConfig.from_dict(fx["config"])
     recs = run_games_batched(cfg, [r["game_index"] for r in fx["games"]], handback=handback)
+    if handback:
+        _assert_handback_ran(dict(runner.LAST_BATCH_PROFILE["timeline"]))
     for got, ref in zip(recs, fx["games"]):
         for k in ("seat_assignment", "winner_ids", "final_scores", "moves_made", "turn_count", "passes",
                   "invalid_actions", "is_tie"):
@@ -177,7 +188,7 @@ def test_batched_arena_matches_bench_strength_reference_records(coop, handback, 
                                                  (99173, "randomized", "0"), (99173, "randomized", "3"),
                                                  (99173, "randomized", "2r"), (99173, "randomized", "2h"),
                                                  (20260301, "round_robin", "3h")])
-def test_device_driver_equals_host_staged_batches(seed, policy, streams):
+def test_device_driver_equals_host_staged_batches(seed, policy, streams, monkeypatch):
     """run_games_batched's device-resident driver (bk_arena_step: positions, tables and
     agent streams stay in HBM; search moves go back as forced moves, FastMCTS inputs come
     from the kernel's stop info) against the host-staged rounds (device_driver=False): every
@@ -188,7 +199,9 @@ def test_device_driver_equals_host_staged_batches(seed, policy, streams):
     "0", one search at a time waited for at once (pipeline=False); "h": each search's move
     handed back as it finishes (ArenaOptions.handback: BK_MCTS_STATE_ROWS agent rows in
     place, bk_mcts_set_done result words in mapped host memory)."""
+    from reinforcementlearning_blokus_amd.arena import runner
     from reinforcementlearning_blokus_amd.arena.runner import run_games_batched
+    monkeypatch.delenv("BK_ARENA_CAPTURE", raising=False)  # a capture directory turns hand-back off
     cfg = RunConfig.from_dict({
         "agents": [{"name": "r", "type": "random"}, {"name": "h", "type": "heuristic"},
                    {"name": "m", "type": "mcts", "params": {"iterations": 12, "max_rollout_moves": 6}},
@@ -198,6 +211,8 @@ def test_device_driver_equals_host_staged_batches(seed, policy, streams):
     dev = run_games_batched(cfg, range(24), pipeline=streams != "0",
                             search_streams=int(streams.rstrip("rh")) if streams != "0" else 1,
                             reserve_cus=16 if streams.endswith("r") else 0, handback=streams.endswith("h"))
+    if streams.endswith("h"):
+        _assert_handback_ran(dict(runner.LAST_BATCH_PROFILE["timeline"]))
     host = run_games_batched(cfg, range(24), device_driver=False)
     for a, b in zip(dev, host):
         for k in RECORD_FIELDS:
