@@ -558,6 +558,66 @@ int bk_mcts_set_done(bk_handle h, uint64_t* done);
 void* bk_host_alloc(size_t bytes);
 int bk_host_free(void* p);
 
+/*
+ * bk_telemetry -- the integers behind engine/telemetry.py:184 collect_all_player_metrics
+ * for n boards, all four players of each, in one launch (added within ABI 7: new symbols
+ * only, nothing existing changed).  states[i] / sets[i]: the position and its frontier
+ * tables; "frontier" below always means the keys of sets[i] (the reference's incrementally
+ * maintained sets, stale entries included), iterated in slot order.  out[4 i + p] is
+ * player p's record; engine/telemetry.py (metrics_from_record) turns it into the
+ * reference's metric dict on the host.
+ * With BK_TEL_STABILITY the kernel also runs simulate_mobility_stability (telemetry.py
+ * :17-77): one random.Random(42) stream per (board, player), CPython 3.10's shuffle of
+ * every opponent's legal list (frontier order) in Player order, the first k_samples
+ * entries placed one at a time and the player's legal moves recounted.
+ */
+#define BK_TEL_STABILITY 1    /* run simulate_mobility_stability's samples */
+#define BK_TEL_MAX_SAMPLES 24 /* 3 opponents x k_samples, k_samples <= 8 */
+#define BK_TEL_MT_OUTPUTS 16384 /* random.Random(42) outputs kept per handle */
+#define BK_TEL_TABLE 50       /* entries of the two effective-frontier tables (0..49) */
+typedef struct bk_telemetry_cfg {
+    int32_t k_samples;   /* TelemetryConfig.MOBILITY_SAMPLES_K = 3 (fast_mode) or 8; 1..8 */
+    int32_t flags;       /* BK_TEL_* */
+    int32_t reserved[2];
+} bk_telemetry_cfg;
+
+typedef struct bk_player_metrics {   /* one per (board, player); POD, 168 bytes */
+    uint32_t mobility;               /* len(get_legal_moves(board, player)) */
+    uint16_t piece_count[21];        /* P_i: legal placements of piece i+1 (mobility_metrics.py:54-59) */
+    uint16_t anchor_max;             /* max over (anchor_row, anchor_col) of moves anchored there (:74-77,122) */
+    uint16_t frontier_size;          /* len(board.get_frontier(player)) = the table's active keys */
+    uint16_t frontier_components;    /* advanced_metrics.py:263-304, Chebyshev distance <= 2 clusters */
+    uint8_t  quadrants;              /* :297-302 */
+    uint8_t  center_dist;            /* compute_center_proximity :69-83 (0..9) */
+    uint16_t dead_self, dead_opp;    /* compute_dead_space_split :104-164 */
+    uint8_t  n_samples;              /* stability samples taken (0 .. 3 * k_samples) */
+    uint8_t  status;                 /* bit0: MT table exhausted; bit1: an opponent list longer than the
+                                        shuffle scratch; bit2: a picked index was not found in the
+                                        opponent's table (tables and planes disagree); any of them:
+                                        stability fields invalid, never silent */
+    uint16_t sample_index[BK_TEL_MAX_SAMPLES];    /* picked index into that opponent's reference-order list */
+    uint16_t sample_mobility[BK_TEL_MAX_SAMPLES]; /* player's legal-move count after that move, in generation
+                                                     order (opponents in Player order, then sample order) */
+    uint32_t rng_draws;              /* 32-bit MT outputs consumed by this player's shuffles */
+    double   effective_frontier;     /* compute_effective_frontier :203-260: the sum in slot order of
+                                        log1p_table[space] * factor_table[v], each product and sum
+                                        rounded once (no FMA) */
+} bk_player_metrics;
+
+/* Both BK_MEM_HOST and BK_MEM_DEVICE (sets 16-byte, states and out 8-byte aligned); n == 0
+   is BK_OK without a launch; launched on the handle's current stream, timed for
+   bk_last_kernel_ms ("k_telemetry"). */
+int bk_telemetry(bk_handle h, const bk_state* states, const bk_fset* sets, int32_t n,
+                 const bk_telemetry_cfg* cfg, bk_player_metrics* out /* n x 4 */, int mem);
+/* The effective-frontier tables of later bk_telemetry calls on h (host pointers, BK_TEL_TABLE
+   doubles each): log1p_table[s] = math.log1p(s), factor_table[v] = 1.0 - min(0.8, 0.2 added
+   v times).  The Python layer passes CPython's own values; NULL for both restores the
+   library's (libm log1p, the same repeated addition).  No GPU call is made. */
+int bk_telemetry_set_tables(bk_handle h, const double* log1p_table, const double* factor_table);
+/* Diagnostics (host only): the first n (<= BK_TEL_MT_OUTPUTS) 32-bit outputs of CPython's
+   random.Random(42) as the kernel indexes them by draw number. */
+int bk_debug_telemetry_mt(uint32_t* out, int32_t n);
+
 /* Average duration (ms) of the most recent bk_rollout/bk_movegen kernel on the handle
    stream, measured with HIP events around that launch. */
 int bk_last_kernel_ms(bk_handle h, float* ms);

@@ -36,6 +36,7 @@ EXPORTS = (
     "bk_mcts", "bk_debug_sections", "bk_pow_half_fix", "bk_debug_fastmcts_select", "bk_arena_advance",
     "bk_arena_step", "bk_mt_cursor_init", "bk_set_tuning", "bk_get_tuning", "bk_debug_fset_op",
     "bk_debug_mcts_failure", "bk_mcts_set_done", "bk_host_alloc", "bk_host_free",
+    "bk_telemetry", "bk_telemetry_set_tables", "bk_debug_telemetry_mt",
 )
 # bk_debug_mcts_failure record (include/blokus_hip.h BK_DIAG_*)
 DIAG_WORDS = 64
@@ -89,6 +90,38 @@ FASTMCTS_OUT_DTYPE = np.dtype([("best_index", "<i4"), ("iterations", "<i4"), ("n
                                ("top_q", "<f8", (10,))])
 assert FASTMCTS_OUT_DTYPE.itemsize == 176
 assert C.sizeof(BkState) == 256 and C.sizeof(BkResult) == 32 and C.sizeof(BkRolloutCfg) == 40
+
+
+class BkTelemetryCfg(C.Structure):
+    _fields_ = [("k_samples", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+TEL_STABILITY = 1         # bk_telemetry_cfg.flags: run simulate_mobility_stability's samples
+TEL_MAX_SAMPLES = 24      # BK_TEL_MAX_SAMPLES
+TEL_MT_OUTPUTS = 16384    # BK_TEL_MT_OUTPUTS
+TEL_TABLE = 50            # BK_TEL_TABLE
+TEL_ST_MT, TEL_ST_LIST, TEL_ST_TABLE = 1, 2, 4  # bk_player_metrics.status bits
+
+
+class BkPlayerMetrics(C.Structure):
+    _fields_ = [("mobility", C.c_uint32), ("piece_count", C.c_uint16 * 21), ("anchor_max", C.c_uint16),
+                ("frontier_size", C.c_uint16), ("frontier_components", C.c_uint16), ("quadrants", C.c_uint8),
+                ("center_dist", C.c_uint8), ("dead_self", C.c_uint16), ("dead_opp", C.c_uint16),
+                ("n_samples", C.c_uint8), ("status", C.c_uint8), ("sample_index", C.c_uint16 * TEL_MAX_SAMPLES),
+                ("sample_mobility", C.c_uint16 * TEL_MAX_SAMPLES), ("rng_draws", C.c_uint32),
+                ("effective_frontier", C.c_double)]
+
+
+PLAYER_METRICS_DTYPE = np.dtype({
+    "names": ["mobility", "piece_count", "anchor_max", "frontier_size", "frontier_components", "quadrants",
+              "center_dist", "dead_self", "dead_opp", "n_samples", "status", "sample_index", "sample_mobility",
+              "rng_draws", "effective_frontier"],
+    "formats": ["<u4", ("<u2", (21,)), "<u2", "<u2", "<u2", "u1", "u1", "<u2", "<u2", "u1", "u1",
+                ("<u2", (TEL_MAX_SAMPLES,)), ("<u2", (TEL_MAX_SAMPLES,)), "<u4", "<f8"],
+    "offsets": [0, 4, 46, 48, 50, 52, 53, 54, 56, 58, 59, 60, 108, 156, 160],
+    "itemsize": 168})
+assert C.sizeof(BkTelemetryCfg) == 16 and C.sizeof(BkPlayerMetrics) == 168
+assert all(getattr(BkPlayerMetrics, n).offset == PLAYER_METRICS_DTYPE.fields[n][1] for n in PLAYER_METRICS_DTYPE.names)
 
 
 class BkMctsCfg(C.Structure):
@@ -197,6 +230,9 @@ def load():
             "bk_mcts_set_done": (C.c_int, [vp, vp]),
             "bk_host_alloc": (C.c_void_p, [C.c_size_t]),
             "bk_host_free": (C.c_int, [vp]),
+            "bk_telemetry": (C.c_int, [vp, vp, vp, C.c_int32, P(BkTelemetryCfg), vp, C.c_int]),
+            "bk_telemetry_set_tables": (C.c_int, [vp, vp, vp]),
+            "bk_debug_telemetry_mt": (C.c_int, [vp, C.c_int32]),
         }
         for name, (res, args) in sigs.items():
             f = getattr(L, name)
@@ -294,6 +330,29 @@ def mt_cursors(seeds) -> np.ndarray:
     out = np.zeros((len(seeds), 4), np.uint32)
     for i, sd in enumerate(seeds.tolist()):
         L.bk_mt_cursor_init(sd, out[i].ctypes.data)
+    return out
+
+
+def telemetry_tables():
+    """(log1p_table, factor_table) of bk_telemetry_set_tables, float64[50] each, with the
+    interpreter's own arithmetic (engine/advanced_metrics.py:244-257 of the reference):
+    math.log1p(space), and 1.0 - min(0.8, vuln) with vuln built by adding 0.2 v times."""
+    import math
+    lt = np.array([math.log1p(i) for i in range(TEL_TABLE)], dtype=np.float64)
+    ft = np.zeros(TEL_TABLE, dtype=np.float64)
+    for v in range(TEL_TABLE):
+        vuln = 0
+        for _ in range(v):
+            vuln += 0.2
+        ft[v] = 1.0 - min(0.8, vuln)
+    return lt, ft
+
+
+def telemetry_mt(n: int = TEL_MT_OUTPUTS) -> np.ndarray:
+    """The first n outputs of random.Random(42) as the library builds them (host only)."""
+    out = np.zeros(n, dtype=np.uint32)
+    if load().bk_debug_telemetry_mt(out.ctypes.data, n) != OK:
+        raise RuntimeError("bk_debug_telemetry_mt failed")
     return out
 
 
@@ -510,6 +569,17 @@ class Handle:
                                        C.c_void_p(masks_ptr), C.c_void_p(quick_ptr), C.c_void_p(forced_ptr),
                                        C.c_void_p(rng_ptr), C.c_void_p(out_ptr), C.c_void_p(stop_ptr), mem)
         self.check(rc, "bk_arena_step")
+
+    def telemetry(self, states_ptr, sets_ptr, n, cfg: BkTelemetryCfg, out_ptr, mem):
+        with self._lock:
+            if not getattr(self, "_tel_tables", False):  # CPython's own log1p / repeated-addition values
+                lt, ft = telemetry_tables()
+                rc = self._L.bk_telemetry_set_tables(self._h, lt.ctypes.data, ft.ctypes.data)
+                self.check(rc, "bk_telemetry_set_tables")
+                self._tel_tables = True
+            rc = self._L.bk_telemetry(self._h, C.c_void_p(states_ptr or 0), C.c_void_p(sets_ptr or 0), n,
+                                      C.byref(cfg), C.c_void_p(out_ptr or 0), mem)
+        self.check(rc, "bk_telemetry")
 
     def advance(self, roots_ptr, n_roots, index_ptr, n, cfg: BkRolloutCfg, seeds_ptr, out_ptr, mem):
         with self._lock:

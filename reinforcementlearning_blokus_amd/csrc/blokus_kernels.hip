@@ -6,6 +6,7 @@
 //   mcts/mcts_agent.py:470-554        MCTSAgent._rollout          (BK_SEM_ROLLOUT)
 //   analytics/tournament/arena_runner.py:652-697 game loop        (BK_SEM_ARENA)
 //   engine/game.py:182-349            game over / GameResult scoring
+//   engine/telemetry.py:17-198        collect_all_player_metrics (bk_telemetry)
 //
 // Design (DESIGN.md has the full story):
 //   * one lane = one board (one game); 64 games per wave, all control flow uniform
@@ -64,6 +65,7 @@
 #define BK_U_MCTS_H 9
 #define BK_U_COOP 10
 #define BK_U_COOP_H 11
+#define BK_U_TELEMETRY 12
 #ifndef BK_TU
 #define BK_TU 0
 #endif
@@ -5254,6 +5256,382 @@ void k_mcts_coop_h(MctsArgs a) { mcts_coop_body<true>(a); }
 __global__ void k_mcts_coop_h(MctsArgs a);
 #endif
 
+// ------------------------------------------------------------------------------------
+// Telemetry: engine/telemetry.py:184 collect_all_player_metrics for batches of boards
+// (bk_telemetry).  One block of four waves per board, wave p working for player p: the
+// wave splits the player's live orientations over its lanes as the cooperative searches
+// do (coop_live_orients / coop_ok_counts / coop_scan), and the board scans (flood fills,
+// frontier clusters) run with board row R in lane R and the neighbour rows fetched by
+// wave shuffles.  Phase A gives every field that needs one board only; after a block
+// barrier (phase B needs the four move counts) each wave runs its player's
+// simulate_mobility_stability: CPython's shuffle of every opponent's list, on a uint16
+// index array in LDS with the random.Random(42) outputs read by draw number from a table
+// the host built, then per pick the move's place in the opponent's frontier-order list
+// (coop_find, locate_move_frontier on a scratch copy of the opponent's rows), the piece
+// ORed into the occupancy, and the player's moves recounted.
+// LDS columns of s_rows (row R of column c at [R * WAVE + c]): 0..3 the players' {B, C}
+// rows, 4..7 each wave's locate scratch, 8..11 each wave's sample board.
+// ------------------------------------------------------------------------------------
+#define TEL_WAVES 4
+#define TEL_SHUF_MAX 2048  // = BK_FASTMCTS_MAX_CHILDREN: the longest list the shuffle scratch holds
+#define TEL_ST_MT 1u
+#define TEL_ST_LIST 2u
+#define TEL_ST_TABLE 4u
+struct TelArgs {
+    const bk_state* states;
+    const bk_fset* sets;
+    int32_t n;
+    int32_t k_samples;
+    int32_t stability;
+    const uint32_t* mt;   // BK_TEL_MT_OUTPUTS outputs of random.Random(42), by draw number
+    const double* tab;    // [0, 50): log1p(space); [50, 100): 1 - min(0.8, vuln) by opponent-frontier count
+    bk_player_metrics* out;
+};
+
+static_assert(sizeof(bk_player_metrics) == 168 && sizeof(bk_player_metrics) % 8 == 0, "the record is copied out as dwords");
+
+struct TelScratch {  // per wave; phase A's counters and phase B's shuffle never live together
+    union {
+        struct {
+            uint32_t anc[BK_CELLS];       // legal moves anchored at each cell
+            double w[BK_FSET_SLOTS];      // effective-frontier weight of each table slot
+        } a;
+        uint16_t shuf[TEL_SHUF_MAX];
+    };
+};
+
+__device__ __forceinline__ void tel_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint32_t tel_wave_sum(uint32_t v, int lane) {
+    return lane_bcast(wave_incl_scan(v, lane), WAVE - 1);
+}
+
+// Flood fill of a 20x20 bit mask held one row per lane (lane R < 20: row R; the other
+// lanes hold 0 and `within` is 0 there): the cells of `within` reachable from `seed`.
+// RAD 1: orthogonal steps; RAD 2: steps of Chebyshev distance <= 2 (the 5x5 box).
+template <int RAD>
+__device__ __forceinline__ uint32_t tel_flood(uint32_t seed, uint32_t within, int lane) {
+    uint32_t cur = seed & within;
+#pragma unroll 1
+    for (int it = 0; it < BK_CELLS; ++it) {  // a fill grows by at least one cell per step
+        uint32_t nx;
+        if constexpr (RAD == 1) {
+            const uint32_t up = __shfl_up(cur, 1), dn = __shfl_down(cur, 1);
+            nx = cur | (cur << 1) | (cur >> 1) | (lane >= 1 ? up : 0u) | (lane < WAVE - 1 ? dn : 0u);
+        } else {
+            const uint32_t h = cur | (cur << 1) | (cur << 2) | (cur >> 1) | (cur >> 2);
+            const uint32_t u1 = __shfl_up(h, 1), u2 = __shfl_up(h, 2), d1 = __shfl_down(h, 1), d2 = __shfl_down(h, 2);
+            nx = h | (lane >= 1 ? u1 : 0u) | (lane >= 2 ? u2 : 0u) | (lane < WAVE - 1 ? d1 : 0u) |
+                 (lane < WAVE - 2 ? d2 : 0u);
+        }
+        nx &= within;
+        if (!__ballot(nx != cur)) break;
+        cur = nx;
+    }
+    return cur;
+}
+
+// compute_frontier_spread's cluster count: components of the frontier cells F under
+// Chebyshev distance <= 2
+__device__ __forceinline__ uint32_t tel_components(uint32_t F, int lane) {
+    uint32_t rem = F, n = 0;
+#pragma unroll 1
+    for (int guard = 0; guard < BK_CELLS; ++guard) {
+        const uint64_t b = __ballot(rem != 0u);
+        if (!b) break;
+        const int L = __ffsll((unsigned long long)b) - 1;
+        const uint32_t seed = lane == L ? (rem & (0u - rem)) : 0u;
+        rem &= ~tel_flood<2>(seed, rem, lane);
+        ++n;
+    }
+    return n;
+}
+
+// one orientation's legal anchors (rows ok) added to the per-cell counters
+__device__ __forceinline__ void tel_anchor_add(uint32_t* anc, const uint32_t (&ok)[20]) {
+    uint64_t P[7] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+#pragma unroll
+    for (int r = 0; r < 20; ++r) {
+        const int off = 20 * r, q = off / 64, sh = off % 64;
+        const uint64_t v = ok[r] & ROWMASK;
+        P[q] |= v << sh;
+        if (sh > 44) P[q + 1] |= v >> (64 - sh);
+    }
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        uint64_t w = P[q];
+        while (w) {
+            const uint32_t x = (uint32_t)__builtin_ctzll(w);
+            w &= w - 1ull;
+            atomicAdd(&anc[64u * (uint32_t)q + x], 1u);
+        }
+    }
+}
+
+#if BK_DEF(BK_U_TELEMETRY)
+__global__ __launch_bounds__(TEL_WAVES * WAVE) void k_telemetry(TelArgs a) {
+    __shared__ __attribute__((aligned(16))) uint2 s_rows[20 * WAVE];
+    __shared__ uint32_t s_own[4][20], s_occ[20], s_fr[4][20];
+    __shared__ uint32_t s_cnt[4][BK_NUM_ORIENTS];  // legal moves per orientation
+    __shared__ uint32_t s_pc[4][BK_PIECES];        // ... per piece
+    __shared__ uint32_t s_mob[4];
+    __shared__ int16_t s_otab[TEL_WAVES][2 * WAVE];
+    __shared__ uint32_t s_mtbuf[TEL_WAVES][WAVE];
+    __shared__ __attribute__((aligned(8))) TelScratch s_scr[TEL_WAVES];
+    __shared__ __attribute__((aligned(8))) bk_player_metrics s_rec[TEL_WAVES];
+    constexpr int REC_WORDS = (int)(sizeof(bk_player_metrics) / 4);
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int p = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const int board = blockIdx.x;  // the grid is exactly n blocks
+    const bk_state* s = a.states + board;
+    const bk_fset* fs = a.sets + board;
+    TelScratch& scr = s_scr[p];
+    bk_player_metrics& rec = s_rec[p];
+
+    for (int i = tid; i < 4 * 20; i += TEL_WAVES * WAVE) {
+        (&s_fr[0][0])[i] = 0u;
+        (&s_own[0][0])[i] = plane_row(s->planes[i / 20], i % 20);
+    }
+    for (int i = tid; i < 4 * BK_NUM_ORIENTS; i += TEL_WAVES * WAVE) (&s_cnt[0][0])[i] = 0u;
+    for (int i = tid; i < 4 * BK_PIECES; i += TEL_WAVES * WAVE) (&s_pc[0][0])[i] = 0u;
+    for (int i = tid; i < TEL_WAVES * REC_WORDS; i += TEL_WAVES * WAVE) reinterpret_cast<bk_u32_alias*>(s_rec)[i] = 0u;
+    for (int i = lane; i < BK_CELLS; i += WAVE) scr.a.anc[i] = 0u;
+    __syncthreads();
+    if (tid < 20) s_occ[tid] = s_own[0][tid] | s_own[1][tid] | s_own[2][tid] | s_own[3][tid];
+    // the player's frontier cells as row masks, from the table's keys
+    int tmask = (int)fs->mask[p];
+    tmask = tmask < BK_FSET_SLOTS ? tmask : BK_FSET_SLOTS - 1;
+    uint32_t fsize = 0;
+    int mykey[4];
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const int sl = lane + WAVE * h;
+        const int k = sl <= tmask ? (int)fs->key[p][sl] : -1;
+        mykey[h] = (k >= 0 && k < BK_CELLS) ? k : -1;
+        if (mykey[h] >= 0) atomicOr(&s_fr[p][k / 20], 1u << (k % 20));
+        fsize += (uint32_t)__popcll(__ballot(mykey[h] >= 0));
+    }
+    __syncthreads();
+
+    // ---- phase A: legal-move counts
+    const bool first = (s->first_move >> p) & 1u;
+    uint2* rows = s_rows + p;
+    {
+        uint32_t own[20], occ[20], B[20], C[20];
+#pragma unroll
+        for (int R = 0; R < 20; ++R) { own[R] = s_own[p][R]; occ[R] = s_occ[R]; }
+        derive_rows(own, occ, first, p, B, C);
+#pragma unroll
+        for (int R = 0; R < 20; ++R) rows[R * WAVE] = make_uint2(B[R], C[R]);
+    }
+    tel_wave_sync();
+    const uint32_t avail = ~s->used[p] & 0x1FFFFFu;
+    int og[2];
+    const uint32_t nlive = coop_live_orients(avail, lane, s_otab[p], og);
+    uint32_t mob;
+    {
+        uint32_t ok0[20], ok1[20], cnt[2];
+        coop_ok_counts(rows, og, nlive, ok0, ok1, cnt);
+        mob = coop_scan(cnt, lane).total;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (og[h] < 0 || !cnt[h]) continue;
+            s_cnt[p][og[h]] = cnt[h];
+            atomicAdd(&s_pc[p][(kInfo[og[h]] & 0xFFu) - 1u], cnt[h]);
+        }
+        tel_anchor_add(scr.a.anc, ok0);
+        tel_anchor_add(scr.a.anc, ok1);
+    }
+    // ---- effective frontier: each slot's weight, then the sum in slot order
+    {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            double wt = 0.0;
+            if (mykey[h] >= 0) {
+                const int r = mykey[h] / 20, c = mykey[h] - 20 * (mykey[h] / 20);
+                const int r0 = r - 3 < 0 ? 0 : r - 3, r1 = r + 3 > 19 ? 19 : r + 3;
+                const int c0 = c - 3 < 0 ? 0 : c - 3, c1 = c + 3 > 19 ? 19 : c + 3;
+                const uint32_t cm = ((2u << c1) - 1u) & ~((1u << c0) - 1u);
+                uint32_t space = 0, v = 0;
+                for (int rr = r0; rr <= r1; ++rr) {
+                    // empty and not beside an own cell = not blocked for the player
+                    space += (uint32_t)__builtin_popcount(~rows[rr * WAVE].x & cm);
+                    uint32_t of = 0u;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) of |= q == p ? 0u : s_fr[q][rr];
+                    v += (uint32_t)__builtin_popcount(of & cm);
+                }
+                wt = __dmul_rn(a.tab[space], a.tab[BK_TEL_TABLE + v]);
+            }
+            scr.a.w[lane + WAVE * h] = wt;
+        }
+    }
+    tel_wave_sync();
+    double eff = 0.0;
+#pragma unroll 1
+    for (int i = 0; i <= tmask; ++i) eff = __dadd_rn(eff, scr.a.w[i]);  // (an unused slot adds 0.0)
+    uint32_t amax = 0;
+    for (int i = lane; i < BK_CELLS; i += WAVE) amax = scr.a.anc[i] > amax ? scr.a.anc[i] : amax;
+#pragma unroll
+    for (int o = WAVE / 2; o; o >>= 1) {
+        const uint32_t t = (uint32_t)__shfl_xor((int)amax, o);
+        amax = t > amax ? t : amax;
+    }
+    // ---- board scans, row R in lane R
+    const bool rl = lane < 20;
+    const int R = rl ? lane : 0;
+    const uint32_t r_own = rl ? s_own[p][R] : 0u, r_occ = rl ? s_occ[R] : 0u;
+    const uint32_t r_fr = rl ? s_fr[p][R] : 0u;
+    const uint32_t r_allfr = rl ? (s_fr[0][R] | s_fr[1][R] | s_fr[2][R] | s_fr[3][R]) : 0u;
+    const uint32_t ncomp = tel_components(r_fr, lane);
+    const uint32_t quads = (__ballot(lane < 10 && (r_fr & 0x3FFu)) ? 1u : 0u) + (__ballot(lane < 10 && (r_fr >> 10)) ? 1u : 0u) +
+                           (__ballot(lane >= 10 && (r_fr & 0x3FFu)) ? 1u : 0u) + (__ballot(lane >= 10 && (r_fr >> 10)) ? 1u : 0u);
+    uint32_t cdist = 9;
+    if (r_own) {
+        const uint32_t lo = r_own & 0x3FFu, hi = r_own >> 10;
+        uint32_t dc = 9;
+        if (lo) dc = 9u - (31u - (uint32_t)__builtin_clz(lo));
+        if (hi) { const uint32_t t = (uint32_t)__builtin_ctz(hi); dc = t < dc ? t : dc; }
+        cdist = (uint32_t)(R <= 9 ? 9 - R : R - 10) + dc;
+        cdist = cdist > 9u ? 9u : cdist;
+    }
+#pragma unroll
+    for (int o = WAVE / 2; o; o >>= 1) {
+        const uint32_t t = (uint32_t)__shfl_xor((int)cdist, o);
+        cdist = t < cdist ? t : cdist;
+    }
+    // dead space: empty cells no frontier cell's region reaches, split by who borders them
+    const uint32_t r_empty = rl ? (~r_occ & ROWMASK) : 0u;
+    const uint32_t r_live = tel_flood<1>(r_allfr, r_empty, lane);
+    const uint32_t r_dead = r_empty & ~r_live;
+    auto beside = [&](uint32_t x) {  // cells orthogonally next to x
+        const uint32_t up = __shfl_up(x, 1), dn = __shfl_down(x, 1);
+        return ((x << 1) | (x >> 1) | (lane >= 1 ? up : 0u) | (lane < WAVE - 1 ? dn : 0u)) & ROWMASK;
+    };
+    const uint32_t r_self = tel_flood<1>(beside(r_own), r_dead, lane);
+    const uint32_t r_rest = r_dead & ~r_self;
+    const uint32_t r_opp = tel_flood<1>(beside(r_occ & ~r_own), r_rest, lane);
+    const uint32_t dself = tel_wave_sum((uint32_t)__builtin_popcount(r_self), lane);
+    const uint32_t dopp = tel_wave_sum((uint32_t)__builtin_popcount(r_opp), lane);
+    if (lane == 0) {
+        rec.mobility = mob;
+        rec.anchor_max = (uint16_t)amax;
+        rec.frontier_size = (uint16_t)fsize;
+        rec.frontier_components = (uint16_t)ncomp;
+        rec.quadrants = (uint8_t)quads;
+        rec.center_dist = (uint8_t)cdist;
+        rec.dead_self = (uint16_t)dself;
+        rec.dead_opp = (uint16_t)dopp;
+        rec.effective_frontier = eff;
+        s_mob[p] = mob;
+    }
+    __syncthreads();  // the four move counts, per-orientation and per-piece counts are complete
+    if (lane < BK_PIECES) rec.piece_count[lane] = (uint16_t)s_pc[p][lane];
+
+    // ---- phase B: simulate_mobility_stability
+    if (a.stability && mob > 0u) {
+        uint32_t draws = 0, bufbase = 0, status = 0, nsamp = 0;
+        s_mtbuf[p][lane] = a.mt[lane];
+        tel_wave_sync();
+        auto next = [&]() -> uint32_t {  // genrand_uint32() by draw number (uniform over the wave)
+            if (draws >= (uint32_t)BK_TEL_MT_OUTPUTS) { status |= TEL_ST_MT; return 0u; }
+            if (draws - bufbase >= (uint32_t)WAVE) {
+                bufbase = draws;
+                tel_wave_sync();
+                s_mtbuf[p][lane] = bufbase + (uint32_t)lane < (uint32_t)BK_TEL_MT_OUTPUTS ? a.mt[bufbase + (uint32_t)lane] : 0u;
+                tel_wave_sync();
+            }
+            return s_mtbuf[p][draws++ - bufbase];
+        };
+        uint16_t* x = scr.shuf;
+#pragma unroll 1
+        for (int q = 0; q < 4 && !status; ++q) {
+            if (q == p) continue;
+            const uint32_t nq = s_mob[q];
+            if (nq == 0u) continue;  // skipped before the shuffle: no draw
+            if (nq > (uint32_t)TEL_SHUF_MAX) { status |= TEL_ST_LIST; break; }
+            tel_wave_sync();
+            for (uint32_t i = (uint32_t)lane; i < nq; i += WAVE) x[i] = (uint16_t)i;
+            tel_wave_sync();
+            // random.shuffle: for i in reversed(range(1, n)): j = _randbelow(i + 1); swap
+#pragma unroll 1
+            for (uint32_t i = nq - 1u; i >= 1u && !status; --i) {
+                const uint32_t nn = i + 1u, sh = (uint32_t)__builtin_clz(nn);  // 32 - nn.bit_length()
+                uint32_t j = next() >> sh;
+                while (j >= nn && !status) j = next() >> sh;
+                if (status) break;
+                if (lane == 0) {
+                    const uint16_t t = x[i];
+                    x[i] = x[j];
+                    x[j] = t;
+                }
+            }
+            tel_wave_sync();
+            if (status) break;
+            // the opponent's per-orientation counts, g ascending over (pass 0, pass 1) lanes
+            const uint32_t cq[2] = {s_cnt[q][lane], lane + WAVE < BK_NUM_ORIENTS ? s_cnt[q][lane + WAVE] : 0u};
+            const int ogq[2] = {lane, lane + WAVE < BK_NUM_ORIENTS ? lane + WAVE : -1};
+            const CoopScan sq = coop_scan(cq, lane);
+            int qmask = (int)fs->mask[q];
+            qmask = qmask < BK_FSET_SLOTS ? qmask : BK_FSET_SLOTS - 1;
+            const uint32_t take = (uint32_t)a.k_samples < nq ? (uint32_t)a.k_samples : nq;
+#pragma unroll 1
+            for (uint32_t j = 0; j < take; ++j) {
+                const uint32_t pick = x[j];
+                uint32_t kk = 0;
+                const int gs = coop_find(sq, ogq, pick, kk);
+                uint2* rq = s_rows + 4 + p;  // locate consumes the C half: a copy of q's rows
+#pragma unroll
+                for (int r = 0; r < 20; ++r) rq[r * WAVE] = s_rows[r * WAVE + q];
+                tel_wave_sync();
+                int ar = -1, ac = 0;
+                locate_move_frontier(gs, kk, rq, fs->key[q], qmask, ar, ac);
+                if (ar < 0) { status |= TEL_ST_TABLE; break; }
+                uint32_t pm[5];
+                int32_t cells[5];
+                piece_cells(gs, ar, ac, pm, cells);
+                uint32_t own[20], occ[20], B[20], C[20];
+#pragma unroll
+                for (int r = 0; r < 20; ++r) {
+                    const int d = r - ar;
+                    const uint32_t m = d == 0 ? pm[0] : d == 1 ? pm[1] : d == 2 ? pm[2] : d == 3 ? pm[3] : d == 4 ? pm[4] : 0u;
+                    own[r] = s_own[p][r];
+                    occ[r] = s_occ[r] | m;
+                }
+                derive_rows(own, occ, first, p, B, C);
+                uint2* rp = s_rows + 8 + p;
+#pragma unroll
+                for (int r = 0; r < 20; ++r) rp[r * WAVE] = make_uint2(B[r], C[r]);
+                tel_wave_sync();
+                uint32_t ok0[20], ok1[20], cnt[2];
+                coop_ok_counts(rp, og, nlive, ok0, ok1, cnt);
+                const uint32_t m2 = coop_scan(cnt, lane).total;
+                if (lane == 0 && nsamp < (uint32_t)BK_TEL_MAX_SAMPLES) {
+                    rec.sample_index[nsamp] = (uint16_t)pick;
+                    rec.sample_mobility[nsamp] = (uint16_t)m2;
+                }
+                ++nsamp;
+                tel_wave_sync();
+            }
+        }
+        if (lane == 0) {
+            rec.n_samples = (uint8_t)(nsamp < (uint32_t)BK_TEL_MAX_SAMPLES ? nsamp : (uint32_t)BK_TEL_MAX_SAMPLES);
+            rec.status = (uint8_t)status;
+            rec.rng_draws = draws;
+        }
+    }
+    tel_wave_sync();
+    bk_u32_alias* dst = reinterpret_cast<bk_u32_alias*>(a.out + ((size_t)board * 4 + (size_t)p));
+    if (lane < REC_WORDS) dst[lane] = reinterpret_cast<const bk_u32_alias*>(&rec)[lane];
+}
+#else
+__global__ void k_telemetry(TelArgs a);
+#endif
+
 #if BK_DEF(BK_U_HOST)
 // ------------------------------------------------------------------------------------
 // C ABI
@@ -5297,6 +5675,11 @@ struct bk_handle_s {
     bool busy = false;
     hipStream_t busy_stream = nullptr;
     bool capturing = false;  // the current launch goes into a graph being captured (untimed)
+    // bk_telemetry: the effective-frontier tables (log1p, factor) then the MT outputs, built on
+    // the host once per handle and uploaded before the first launch (again when the tables change)
+    void* d_tel = nullptr;
+    double tel_tab[2 * BK_TEL_TABLE] = {0};
+    bool tel_tab_set = false, tel_dirty = true;
 };
 
 static const char* const kTuneNames[BK_TUNE_COUNT] = {
@@ -5466,7 +5849,8 @@ int bk_destroy(bk_handle h) {
     if (h->busy) (void)hipStreamSynchronize(h->busy_stream);
     if (h->own) (void)hipStreamSynchronize(h->own);
     void* bufs[] = {h->d_in, h->d_out, h->d_aux, h->d_aux2, h->d_slab, h->d_fin, h->d_fout, h->d_fslab,
-                    h->d_mc, h->d_mclane, h->d_step, h->d_counter, h->d_rh, h->d_diag, h->d_started, h->d_mtwork};
+                    h->d_mc, h->d_mclane, h->d_step, h->d_counter, h->d_rh, h->d_diag, h->d_started, h->d_mtwork,
+                    h->d_tel};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -5989,6 +6373,124 @@ int bk_mt_cursor_init(uint32_t seed, uint32_t* out4) {
         if (j == 1) b = x;
     }
     out4[0] = 0; out4[1] = seed; out4[2] = b; out4[3] = x;
+    return BK_OK;
+}
+
+// CPython's random.Random(42): init_by_array({42}) (Modules/_randommodule.c), then tempered
+// genrand_uint32 outputs in order
+static void tel_mt_outputs(uint32_t* out, int n) {
+    uint32_t mt[624];
+    mt[0] = 19650218u;
+    for (uint32_t i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + i;
+    const uint32_t key[1] = {42u};
+    uint32_t i = 1, j = 0;
+    for (int k = 624; k; --k) {
+        mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1664525u)) + key[j] + j;
+        ++i; ++j;
+        if (i >= 624) { mt[0] = mt[623]; i = 1; }
+        if (j >= 1) j = 0;
+    }
+    for (int k = 623; k; --k) {
+        mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1566083941u)) - i;
+        ++i;
+        if (i >= 624) { mt[0] = mt[623]; i = 1; }
+    }
+    mt[0] = 0x80000000u;
+    int idx = 624;
+    for (int o = 0; o < n; ++o) {
+        if (idx >= 624) {
+            for (int kk = 0; kk < 624; ++kk) {
+                const uint32_t y = (mt[kk] & 0x80000000u) | (mt[(kk + 1) % 624] & 0x7FFFFFFFu);
+                mt[kk] = mt[(kk + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908B0DFu : 0u);
+            }
+            idx = 0;
+        }
+        uint32_t y = mt[idx++];
+        y ^= y >> 11;
+        y ^= (y << 7) & 0x9D2C5680u;
+        y ^= (y << 15) & 0xEFC60000u;
+        y ^= y >> 18;
+        out[o] = y;
+    }
+}
+
+int bk_debug_telemetry_mt(uint32_t* out, int32_t n) {
+    if (!out || n < 0 || n > BK_TEL_MT_OUTPUTS) return BK_EINVAL;
+    tel_mt_outputs(out, n);
+    return BK_OK;
+}
+
+int bk_telemetry_set_tables(bk_handle h, const double* log1p_table, const double* factor_table) {
+    if (!h || (log1p_table == nullptr) != (factor_table == nullptr))
+        return set_err(h, BK_EINVAL, "bk_telemetry_set_tables: both tables or neither%s", "");
+    h->tel_tab_set = log1p_table != nullptr;
+    if (log1p_table) {
+        memcpy(h->tel_tab, log1p_table, sizeof(double) * BK_TEL_TABLE);
+        memcpy(h->tel_tab + BK_TEL_TABLE, factor_table, sizeof(double) * BK_TEL_TABLE);
+    }
+    h->tel_dirty = true;
+    return BK_OK;
+}
+
+int bk_telemetry(bk_handle h, const bk_state* states, const bk_fset* sets, int32_t n, const bk_telemetry_cfg* cfg,
+                 bk_player_metrics* out, int mem) {
+    if (!h || !states || !sets || !cfg || !out || n < 0 || (mem != BK_MEM_HOST && mem != BK_MEM_DEVICE))
+        return set_err(h, BK_EINVAL, "bk_telemetry: invalid arguments%s", "");
+    if (cfg->k_samples < 1 || cfg->k_samples > 8)
+        return set_err(h, BK_EINVAL, "bk_telemetry: k_samples must be 1..8%s", "");
+    if (cfg->flags & ~BK_TEL_STABILITY) return set_err(h, BK_EINVAL, "bk_telemetry: unknown flags%s", "");
+    if (n == 0) return BK_OK;
+    if (mem == BK_MEM_DEVICE && (((uintptr_t)sets & 15) || ((uintptr_t)states & 7) || ((uintptr_t)out & 7)))
+        return set_err(h, BK_EINVAL, "bk_telemetry: sets must be 16-byte, states and out 8-byte aligned%s", "");
+    HIPCHK(h, hipSetDevice(h->device));
+    BK_IDLE(h, "bk_telemetry");
+    const size_t tab_bytes = sizeof(double) * 2 * BK_TEL_TABLE;
+    if (!h->d_tel) {
+        HIPCHK(h, hipMalloc(&h->d_tel, tab_bytes + sizeof(uint32_t) * BK_TEL_MT_OUTPUTS));
+        h->tel_dirty = true;
+    }
+    if (h->tel_dirty) {
+        if (!h->tel_tab_set) {  // the library's own tables: libm log1p (what math.log1p calls)
+            for (int i = 0; i < BK_TEL_TABLE; ++i) {
+                h->tel_tab[i] = log1p((double)i);
+                volatile double vuln = 0.0;  // built by repeated addition, as the reference does
+                for (int k = 0; k < i; ++k) vuln = vuln + 0.2;
+                const double capped = vuln < 0.8 ? vuln : 0.8;
+                h->tel_tab[BK_TEL_TABLE + i] = 1.0 - capped;
+            }
+        }
+        std::vector<uint32_t> mt(BK_TEL_MT_OUTPUTS);
+        tel_mt_outputs(mt.data(), BK_TEL_MT_OUTPUTS);
+        HIPCHK(h, hipMemcpyAsync(h->d_tel, h->tel_tab, tab_bytes, hipMemcpyHostToDevice, h->cur));
+        HIPCHK(h, hipMemcpyAsync((char*)h->d_tel + tab_bytes, mt.data(), sizeof(uint32_t) * BK_TEL_MT_OUTPUTS,
+                                 hipMemcpyHostToDevice, h->cur));
+        HIPCHK(h, hipStreamSynchronize(h->cur));  // the staging vector leaves scope
+        h->tel_dirty = false;
+    }
+    void *d_states, *d_sets;
+    int rc = stage_in(h, states, sizeof(bk_state) * (size_t)n, mem, &d_states, &h->d_in, &h->d_in_cap);
+    if (rc) return rc;
+    rc = stage_in(h, sets, sizeof(bk_fset) * (size_t)n, mem, &d_sets, &h->d_fin, &h->d_fin_cap);
+    if (rc) return rc;
+    const size_t out_bytes = sizeof(bk_player_metrics) * 4 * (size_t)n;
+    bk_player_metrics* d_outp = out;
+    if (mem == BK_MEM_HOST) {
+        rc = grow(h, &h->d_out, &h->d_out_cap, out_bytes);
+        if (rc) return rc;
+        d_outp = (bk_player_metrics*)h->d_out;
+    }
+    TelArgs a{(const bk_state*)d_states, (const bk_fset*)d_sets, n, cfg->k_samples,
+              (cfg->flags & BK_TEL_STABILITY) ? 1 : 0, (const uint32_t*)((char*)h->d_tel + tab_bytes),
+              (const double*)h->d_tel, d_outp};
+    HIPCHK(h, mark_start(h));
+    h->last_kernel = "k_telemetry";
+    hipLaunchKernelGGL(k_telemetry, dim3(n), dim3(TEL_WAVES * WAVE), 0, h->cur, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, mark_end(h));
+    if (mem == BK_MEM_HOST) {
+        HIPCHK(h, hipMemcpyAsync(out, d_outp, out_bytes, hipMemcpyDeviceToHost, h->cur));
+        HIPCHK(h, hipStreamSynchronize(h->cur));
+    }
     return BK_OK;
 }
 

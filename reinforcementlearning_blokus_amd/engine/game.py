@@ -1,8 +1,11 @@
 """BlokusGame on top of the GPU move generator (reference: engine/game.py).
 
 Scoring, game-over and result semantics follow engine/game.py:57-349.  The
-reference's per-move telemetry (engine/telemetry.py, ~80x the cost of a move) is UI
-analytics outside the hot path: ``enable_telemetry`` is accepted and ignored.
+reference's per-move telemetry (engine/telemetry.py, ~80x the cost of a move there) is
+opt-in here: with ``BlokusGame.telemetry_backend = "gpu"`` and ``enable_telemetry``,
+make_move collects the metrics before and after the move (one bk_telemetry launch each,
+engine/telemetry.py) and attaches the reference's ``telemetry`` block to the history
+entry; with the default ``None`` the argument is accepted and nothing is collected.
 ``move_generator.has_legal_moves`` is looked up on the instance each time, so tests
 can patch it exactly as the reference's tests do (tests/test_game_over_logic.py:31).
 """
@@ -41,13 +44,15 @@ def _piece_penalty(used) -> int:
 
 
 class BlokusGame:
+    telemetry_backend = None  # "gpu": per-move telemetry through bk_telemetry (needs enable_telemetry)
+
     def __init__(self, enable_telemetry: bool = True, telemetry_fast_mode: bool = True):
         self.board = Board()
         self.move_generator: LegalMoveGenerator = get_shared_generator()
         self.piece_generator = PieceGenerator()
         self.game_history = []
         self.winner = None
-        self.enable_telemetry = enable_telemetry  # accepted; telemetry is out of scope
+        self.enable_telemetry = enable_telemetry  # collected only with telemetry_backend = "gpu"
         self.telemetry_fast_mode = telemetry_fast_mode
 
     def make_move(self, move: Move, player: Optional[Player] = None) -> bool:
@@ -56,6 +61,8 @@ class BlokusGame:
             player = self.board.current_player
         if not self.move_generator.is_move_legal(self.board, player, move):
             return False
+        telemetry_on = self.enable_telemetry and self.telemetry_backend == "gpu"
+        before = self._collect_telemetry() if telemetry_on else None
         rel = self.move_generator.piece_position_cache[move.piece_id][move.orientation]
         cells = [Position(move.anchor_row + r, move.anchor_col + c) for r, c in rel]
         ok = self.board.place_piece(cells, player, move.piece_id, validate=False)
@@ -77,8 +84,25 @@ class BlokusGame:
                                                  for p in Player},
                             "influence_map": None},
             })
+            if telemetry_on and before:
+                after = self._collect_telemetry()
+                if after:
+                    from .telemetry import move_telemetry
+                    payload = move_telemetry(idx + 1, player, move, before, after)
+                    if payload:
+                        self.game_history[-1]["telemetry"] = payload
             self._check_game_over()
         return ok
+
+    def _collect_telemetry(self):
+        """Metrics of the current board, or None with a warning if the launch failed (a
+        telemetry failure never blocks the move, as in the reference)."""
+        from .telemetry import collect_all_player_metrics
+        try:
+            return collect_all_player_metrics(self.board, self.move_generator, self.telemetry_fast_mode)
+        except Exception as e:  # noqa: BLE001
+            logger.warning("telemetry failed: %s", e)
+            return None
 
     def _check_game_over(self) -> None:
         """Over iff no player has a legal move (engine/game.py:182-214)."""

@@ -157,6 +157,32 @@ class BlokusGPU:
                                  N.MEM_HOST)
         return cnt, out
 
+    def telemetry(self, states, sets, *, k_samples: int = 3, stability: bool = True):
+        """The integers behind the reference's collect_all_player_metrics for n boards
+        (bk_telemetry): states as movegen, sets the boards' frontier tables (FSET_DTYPE[n] /
+        uint8[n,2080], host or torch cuda).  Returns records [n, 4] of
+        N.PLAYER_METRICS_DTYPE (torch in: a uint8 cuda tensor [n, 4, 168]);
+        engine.telemetry.metrics_from_record turns one into the metric dict."""
+        cfg = N.BkTelemetryCfg(int(k_samples), N.TEL_STABILITY if stability else 0)
+        item = N.PLAYER_METRICS_DTYPE.itemsize
+        if _is_torch(states):
+            import torch
+            n = states.shape[0]
+            _check_device_tensor(states, "states", torch.uint8, (n, 256), self.device)
+            _check_device_tensor(sets, "sets", torch.uint8, (n, N.FSET_DTYPE.itemsize), self.device)
+            out = torch.empty((n, 4, item), dtype=torch.uint8, device=states.device)
+            self._stream_from_torch()
+            self.handle.telemetry(states.data_ptr(), sets.data_ptr(), n, cfg, out.data_ptr(), N.MEM_DEVICE)
+            return out
+        st = np.ascontiguousarray(states).view(np.uint8)
+        fs = np.ascontiguousarray(sets).view(np.uint8)
+        n = st.size // 256
+        st, fs = st.reshape(n, 256), fs.reshape(n, N.FSET_DTYPE.itemsize)
+        out = np.zeros((n, 4), dtype=N.PLAYER_METRICS_DTYPE)
+        self.handle.set_stream(None)
+        self.handle.telemetry(st.ctypes.data, fs.ctypes.data, n, cfg, out.ctypes.data, N.MEM_HOST)
+        return out
+
     def has_moves(self, states):
         """uint8 mask per state: bit p set iff player p has a legal move (move_generator.py:961)."""
         if _is_torch(states):
