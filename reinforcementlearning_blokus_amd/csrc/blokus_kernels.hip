@@ -720,7 +720,9 @@ __device__ __forceinline__ void locate_move_frontier(const OrientRow& orow, uint
     }
     // Pass 2 reads the table 16 slots per pair of uint4 loads into registers, all
     // indices static (a dynamically indexed key array would live in scratch memory); the
-    // next 16 slots' loads are issued before this batch is walked.  Per frontier cell f =
+    // next 16 slots' loads are issued before this batch is used.  Tables of <= 128 slots
+    // keep only a mask of their live slots from that pass and then load each live key by
+    // its own address; 256-slot tables walk the batches themselves.  Per frontier cell f =
     // (fr, fc) the new anchors of piece row d (anchor row fr - d) are the legal, not yet
     // counted anchors among columns fc - c of the row's cells: one LDS row read and a mask
     // (rev[d] has bit 4 - c per cell (d, c); (rev[d] << fc) >> 4 puts them at fc - c).
@@ -737,44 +739,107 @@ __device__ __forceinline__ void locate_move_frontier(const OrientRow& orow, uint
     uint32_t cnt = 0;
     int hit_f = -1;
     const bk_u4_alias* k4 = reinterpret_cast<const bk_u4_alias*>(key);
-    uint4 qa = k4[0], qb = k4[1];  // tables hold >= 8 slots; the storage has 256
-#pragma unroll 1
-    for (int b0 = 0; b0 <= mask && hit_f < 0; b0 += 16) {
-        const int nb0 = b0 + 16 <= mask ? b0 + 16 : b0;
-        const uint4 na = k4[(nb0 >> 4) * RS], nb = k4[(nb0 >> 4) * RS + 1];
-        const uint32_t w[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-        // the batch's slots that can add an anchor, then one divergent pass over just
-        // those: the wave runs the row reads max-over-lanes-of-relevant-slots times
-        uint32_t rel = 0;
+    // one relevant frontier cell f: count its new anchors and claim them, or stop at f
+    // when they hold the kk-th
+    auto count_key = [&](int f) {
+        const int fr = (int)((uint32_t)f * 3277u >> 16), fc = f - 20 * fr;  // f / 20 for 0 <= f < 400
+        uint32_t hm[5], tot = 0;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int f = (int)(int16_t)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu));
-            const int fr = f >= 0 ? f / 20 : 0;
-            rel |= (f >= 0 && b0 + j <= mask && ((arows >> (fr + 5 - H)) & hmask)) ? (1u << j) : 0u;
+        for (int d = 0; d < 5; ++d) {
+            const int ar = fr - d;
+            hm[d] = (d < H && ar >= 0) ? (rows[(ar < 0 ? 0 : ar) * WAVE].y & ((rev[d] << fc) >> 4)) : 0u;
+            tot += __builtin_popcount(hm[d]);
         }
+        if (cnt + tot > kk) { hit_f = f; return; }
+#pragma unroll
+        for (int d = 0; d < 5; ++d)
+            if (hm[d]) rows[(fr - d) * WAVE].y &= ~hm[d];
+        cnt += tot;
+    };
+    if (mask >= 128) {
+        // 256-slot tables (rare): every slot is tested, 16 per pair of uint4 loads
+        uint4 qa = k4[0], qb = k4[1];
 #pragma unroll 1
-        while (rel && hit_f < 0) {
-            const int j = __builtin_ctz(rel);
-            rel &= rel - 1u;
-            uint32_t wj = w[0];
+        for (int b0 = 0; b0 <= mask && hit_f < 0; b0 += 16) {
+            const int nb0 = b0 + 16 <= mask ? b0 + 16 : b0;
+            const uint4 na = k4[(nb0 >> 4) * RS], nb = k4[(nb0 >> 4) * RS + 1];
+            const uint32_t w[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+            // the batch's slots that can add an anchor, then one divergent pass over just
+            // those: the wave runs the row reads max-over-lanes-of-relevant-slots times
+            uint32_t rel = 0;
 #pragma unroll
-            for (int q = 1; q < 8; ++q) wj = (j >> 1) == q ? w[q] : wj;
-            const int f = (int)(int16_t)((j & 1) ? (wj >> 16) : (wj & 0xFFFFu));
-            const int fr = f / 20, fc = f - 20 * fr;
-            uint32_t hm[5], tot = 0;
-#pragma unroll
-            for (int d = 0; d < 5; ++d) {
-                const int ar = fr - d;
-                hm[d] = (d < H && ar >= 0) ? (rows[(ar < 0 ? 0 : ar) * WAVE].y & ((rev[d] << fc) >> 4)) : 0u;
-                tot += __builtin_popcount(hm[d]);
+            for (int j = 0; j < 16; ++j) {
+                const int f = (int)(int16_t)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu));
+                const int fr = f >= 0 ? f / 20 : 0;
+                rel |= (f >= 0 && b0 + j <= mask && ((arows >> (fr + 5 - H)) & hmask)) ? (1u << j) : 0u;
             }
-            if (cnt + tot > kk) { hit_f = f; continue; }
+#pragma unroll 1
+            while (rel && hit_f < 0) {
+                const int j = __builtin_ctz(rel);
+                rel &= rel - 1u;
+                uint32_t wj = w[0];
 #pragma unroll
-            for (int d = 0; d < 5; ++d)
-                if (hm[d]) rows[(fr - d) * WAVE].y &= ~hm[d];
-            cnt += tot;
+                for (int q = 1; q < 8; ++q) wj = (j >> 1) == q ? w[q] : wj;
+                count_key((int)(int16_t)((j & 1) ? (wj >> 16) : (wj & 0xFFFFu)));
+            }
+            qa = na; qb = nb;
         }
-        qa = na; qb = nb;
+    } else {
+        // Tables of <= 128 slots (CPython keeps them at least 4x the live keys, so most
+        // slots are empty): the sign bits of the 16-bit slots give a 128-bit mask of the
+        // live slots (FS_UNUSED and FS_DUMMY are negative), and each lane then walks just
+        // its own live slots, in slot order and in step with no other lane's table.
+        // lm[0] bit 0 is the lowest slot not yet taken, slot lbase: a drained word is
+        // shifted out, so the next slot always comes from lm[0] (all indices static).
+        uint32_t lm[4] = {0u, 0u, 0u, 0u};
+        {
+            uint4 qa = k4[0], qb = k4[1];  // tables hold >= 8 slots; the storage has 256
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                if (b * 16 <= mask) {
+                    uint4 na = qa, nb = qb;
+                    if (b < 7) {
+                        const int nx = (b + 1) * 16 <= mask ? b + 1 : b;
+                        na = k4[nx * RS];
+                        nb = k4[nx * RS + 1];
+                    }
+                    const uint32_t w[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+                    uint32_t dead = 0;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) dead |= (((w[i] >> 15) & 1u) | ((w[i] >> 30) & 2u)) << (2 * i);
+                    const uint32_t valid = (b == 0 && mask < 15) ? 0xFFu : 0xFFFFu;
+                    lm[b >> 1] |= (~dead & valid) << ((b & 1) * 16);
+                    qa = na; qb = nb;
+                }
+            }
+        }
+        int lbase = 0;
+        // the next live slot's key (-1: none left, or a drained word was shifted out)
+        auto next_key = [&]() {
+            const bool z = lm[0] == 0u;
+            lm[0] = z ? lm[1] : lm[0];
+            lm[1] = z ? lm[2] : lm[1];
+            lm[2] = z ? lm[3] : lm[2];
+            lm[3] = z ? 0u : lm[3];
+            lbase += z ? 32 : 0;
+            const bool have = lm[0] != 0u;
+            const int s = have ? lbase + __builtin_ctz(lm[0] | 0x80000000u) : 0;
+            lm[0] &= lm[0] - 1u;
+            const int16_t v = key[RS == 2 ? s : (s >> 4) * (RS * 8) + (s & 15)];
+            return have ? (int)v : -1;
+        };
+        // The next key's load is in flight while one key is counted.  More keys in
+        // flight, or keys taken in groups with a compaction of the group's relevant
+        // ones, measured slower: the kernel is bound by the instructions it
+        // issues, not by this load's latency.
+        int nxt = next_key();
+#pragma unroll 1
+        for (;;) {
+            const int f = nxt;
+            nxt = next_key();
+            if (f >= 0 && ((arows >> (((uint32_t)f * 3277u >> 16) + 5 - H)) & hmask)) count_key(f);
+            if (hit_f >= 0 || (nxt < 0 && !(lm[0] | lm[1] | lm[2] | lm[3]))) break;
+        }
     }
     int found_r = -1, found_c = 0;
     if (hit_f >= 0) {  // the (kk - cnt)-th new anchor of frontier cell hit_f, in cell order
