@@ -618,6 +618,57 @@ int bk_telemetry_set_tables(bk_handle h, const double* log1p_table, const double
    random.Random(42) as the kernel indexes them by draw number. */
 int bk_debug_telemetry_mt(uint32_t* out, int32_t n);
 
+/*
+ * bk_snapshot_features -- the win-probability snapshot rows of analytics/winprob/features.py
+ * (build_snapshot_runtime_context + extract_player_snapshot_features) for n boards, all four
+ * players of each, in one launch (added within ABI 7: new symbols only).  states[i] / sets[i]
+ * as bk_telemetry: "frontier" always means the keys of sets[i], stale entries included.
+ * turn_index[i] is the arena's turn_count at the capture (arena_runner.py:536-539), max_turns
+ * the run's; the ply is states[i].move_count.
+ * rec[4 i + p] holds the integers behind player p's row.  features[(4 i + p) * 34 + c] is column
+ * c of that row in SNAPSHOT_FEATURE_COLUMNS order (features.py:23-58), computed on the device
+ * with one correctly rounded operation per reference operation, in the reference's order
+ * (P_i / O_i, then * S_i, summed by ascending piece id; count / 400; used / 21.0;
+ * turn_index / max(1, max_turns); move_count / max(1, max_turns)), so the doubles are
+ * CPython's bit for bit.
+ */
+#define BK_SNAPSHOT_COLUMNS 34
+#define BK_SNAP_ST_TABLE 1u /* status: a frontier table's mask is >= BK_FSET_SLOTS or an active slot holds a
+                               key >= BK_CELLS: the table was read clamped, frontier-derived fields
+                               (frontier_size(s), corner_differential, deadzone_count) are not to be trusted */
+#define BK_SNAP_ST_STATE 2u /* status: two players' planes overlap, a plane has bits beyond cell 399 or a used
+                               mask bits beyond piece 21: the state is no Blokus position */
+typedef struct bk_snapshot_rec {     /* one per (board, player); POD, 80 bytes, no padding */
+    uint32_t mobility;               /*  0: len(get_legal_moves(board, player))                          */
+    uint16_t piece_count[21];        /*  4: P_i, legal placements of piece i+1 (as bk_player_metrics)     */
+    uint16_t frontier_size;          /* 46: len(board.get_frontier(player)) = the table's active keys     */
+    uint16_t frontier_sizes[4];      /* 48: the same for players 0..3                                     */
+    int16_t  corner_differential;    /* 56: advanced_metrics.py:8-15, own - sum of the opponents'         */
+    uint16_t opponent_adjacency;     /* 58: :86-101, own cells orthogonally beside another player's cell  */
+    uint16_t deadzone_count;         /* 60: :167-200, cells of empty 4-connected components that hold no
+                                            frontier key of any player (board-wide: equal in the 4 records) */
+    uint16_t occupied_cells;         /* 62: np.count_nonzero(board.grid)                                  */
+    uint16_t own_cells;              /* 64: np.count_nonzero(board.grid == player.value)                  */
+    uint8_t  center_dist;            /* 66: compute_center_proximity :69-83 (0..9)                        */
+    uint8_t  used_count;             /* 67: len(board.player_pieces_used[player])                         */
+    uint32_t opp_moves_sum;          /* 68: sum of the three opponents' legal-move counts                 */
+    uint16_t move_count;             /* 72: states[i].move_count (phase_ply)                              */
+    uint8_t  status;                 /* 74: 0 or BK_SNAP_ST_* bits; never silently wrong                  */
+    uint8_t  reserved;               /* 75: 0                                                             */
+    int32_t  turn_index;             /* 76: turn_index[i] as given                                        */
+} bk_snapshot_rec;
+
+/* rec (n x 4) and features (n x 4 x BK_SNAPSHOT_COLUMNS doubles) may each be NULL, not both.
+   Both BK_MEM_HOST and BK_MEM_DEVICE (device pointers: sets 16-byte, states, rec and features
+   8-byte, turn_index 4-byte aligned, else BK_EINVAL); BK_EINVAL too for null states, sets or
+   turn_index and max_turns < 0; n == 0 is BK_OK without a launch; launched on the handle's
+   current stream, timed for bk_last_kernel_ms ("k_snapshot"). */
+int bk_snapshot_features(bk_handle h, const bk_state* states, const bk_fset* sets, int32_t n,
+                         const int32_t* turn_index, int32_t max_turns, bk_snapshot_rec* rec,
+                         double* features, int mem);
+/* sizeof(bk_snapshot_rec) as the library was compiled (binding checks; no GPU call). */
+int bk_snapshot_rec_size(void);
+
 /* Average duration (ms) of the most recent bk_rollout/bk_movegen kernel on the handle
    stream, measured with HIP events around that launch. */
 int bk_last_kernel_ms(bk_handle h, float* ms);

@@ -37,6 +37,7 @@ EXPORTS = (
     "bk_arena_step", "bk_mt_cursor_init", "bk_set_tuning", "bk_get_tuning", "bk_debug_fset_op",
     "bk_debug_mcts_failure", "bk_mcts_set_done", "bk_host_alloc", "bk_host_free",
     "bk_telemetry", "bk_telemetry_set_tables", "bk_debug_telemetry_mt",
+    "bk_snapshot_features", "bk_snapshot_rec_size",
 )
 # bk_debug_mcts_failure record (include/blokus_hip.h BK_DIAG_*)
 DIAG_WORDS = 64
@@ -122,6 +123,31 @@ PLAYER_METRICS_DTYPE = np.dtype({
     "itemsize": 168})
 assert C.sizeof(BkTelemetryCfg) == 16 and C.sizeof(BkPlayerMetrics) == 168
 assert all(getattr(BkPlayerMetrics, n).offset == PLAYER_METRICS_DTYPE.fields[n][1] for n in PLAYER_METRICS_DTYPE.names)
+
+
+SNAPSHOT_COLUMNS = 34           # BK_SNAPSHOT_COLUMNS
+SNAP_ST_TABLE, SNAP_ST_STATE = 1, 2  # bk_snapshot_rec.status bits
+
+
+class BkSnapshotRec(C.Structure):
+    _fields_ = [("mobility", C.c_uint32), ("piece_count", C.c_uint16 * 21), ("frontier_size", C.c_uint16),
+                ("frontier_sizes", C.c_uint16 * 4), ("corner_differential", C.c_int16),
+                ("opponent_adjacency", C.c_uint16), ("deadzone_count", C.c_uint16), ("occupied_cells", C.c_uint16),
+                ("own_cells", C.c_uint16), ("center_dist", C.c_uint8), ("used_count", C.c_uint8),
+                ("opp_moves_sum", C.c_uint32), ("move_count", C.c_uint16), ("status", C.c_uint8),
+                ("reserved", C.c_uint8), ("turn_index", C.c_int32)]
+
+
+SNAPSHOT_REC_DTYPE = np.dtype({
+    "names": ["mobility", "piece_count", "frontier_size", "frontier_sizes", "corner_differential",
+              "opponent_adjacency", "deadzone_count", "occupied_cells", "own_cells", "center_dist", "used_count",
+              "opp_moves_sum", "move_count", "status", "reserved", "turn_index"],
+    "formats": ["<u4", ("<u2", (21,)), "<u2", ("<u2", (4,)), "<i2", "<u2", "<u2", "<u2", "<u2", "u1", "u1", "<u4",
+                "<u2", "u1", "u1", "<i4"],
+    "offsets": [0, 4, 46, 48, 56, 58, 60, 62, 64, 66, 67, 68, 72, 74, 75, 76],
+    "itemsize": 80})
+assert C.sizeof(BkSnapshotRec) == 80
+assert all(getattr(BkSnapshotRec, n).offset == SNAPSHOT_REC_DTYPE.fields[n][1] for n in SNAPSHOT_REC_DTYPE.names)
 
 
 class BkMctsCfg(C.Structure):
@@ -233,6 +259,8 @@ def load():
             "bk_telemetry": (C.c_int, [vp, vp, vp, C.c_int32, P(BkTelemetryCfg), vp, C.c_int]),
             "bk_telemetry_set_tables": (C.c_int, [vp, vp, vp]),
             "bk_debug_telemetry_mt": (C.c_int, [vp, C.c_int32]),
+            "bk_snapshot_features": (C.c_int, [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int]),
+            "bk_snapshot_rec_size": (C.c_int, []),
         }
         for name, (res, args) in sigs.items():
             f = getattr(L, name)
@@ -580,6 +608,13 @@ class Handle:
             rc = self._L.bk_telemetry(self._h, C.c_void_p(states_ptr or 0), C.c_void_p(sets_ptr or 0), n,
                                       C.byref(cfg), C.c_void_p(out_ptr or 0), mem)
         self.check(rc, "bk_telemetry")
+
+    def snapshot_features(self, states_ptr, sets_ptr, n, turn_ptr, max_turns, rec_ptr, feat_ptr, mem):
+        with self._lock:
+            rc = self._L.bk_snapshot_features(self._h, C.c_void_p(states_ptr or 0), C.c_void_p(sets_ptr or 0), n,
+                                              C.c_void_p(turn_ptr or 0), int(max_turns), C.c_void_p(rec_ptr or 0),
+                                              C.c_void_p(feat_ptr or 0), mem)
+        self.check(rc, "bk_snapshot_features")
 
     def advance(self, roots_ptr, n_roots, index_ptr, n, cfg: BkRolloutCfg, seeds_ptr, out_ptr, mem):
         with self._lock:

@@ -40,8 +40,11 @@ class AgentConfig:
 
 @dataclass(frozen=True)
 class SnapshotConfig:
-    """Snapshot datasets (ML features) are outside the hot path: only ``enabled=False``
-    is supported; the field is kept so reference configs load unchanged."""
+    """Snapshot datasets (:90-123): with ``enabled`` the arena captures, at the fixed plies
+    ``checkpoints``, one row of win-probability features per player (analytics/winprob) and
+    run_experiment writes them as snapshots.csv.  All-random runs replay their games on the
+    GPU to each checkpoint; every other seating plays in the host loop (run_single_game),
+    the batched mixed-agent paths do not capture yet."""
     enabled: bool = False
     strategy: str = "fixed_ply"
     checkpoints: List[int] = field(default_factory=lambda: list(DEFAULT_SNAPSHOT_PLYS))
@@ -57,8 +60,6 @@ class SnapshotConfig:
     def validate(self) -> None:
         if self.strategy != "fixed_ply":
             raise ValueError(f"Unsupported snapshot strategy '{self.strategy}'. Supported values: ['fixed_ply'].")
-        if self.enabled:
-            raise ValueError("snapshot datasets are not supported by the GPU arena (out of scope)")
 
     def to_dict(self) -> Dict[str, Any]:
         return {"enabled": self.enabled, "strategy": self.strategy, "checkpoints": list(self.checkpoints)}

@@ -5,9 +5,16 @@ the frontier-order playout kernel, started from the empty board with each seat's
 RandomAgent seed (``_agent_seed``), so its record equals ``run_single_game``'s for the
 same run seed and game index.  ``run_single_game`` is the reference loop itself
 (:578-777) over the GPU-backed ``BlokusGame`` for every other seating.
+
+With ``snapshots.enabled`` both paths also produce the reference's win-probability rows
+(:522-575, :625-650, :722-731), appended to the list passed as ``snapshot_rows``: the host
+loop captures positions at the checkpoints and ``run_games_gpu`` replays the games to each
+checkpoint; either way the features come from bk_snapshot_features launches
+(``SnapshotBatch``).  ``run_experiment`` writes them as snapshots.csv.
 """
 from __future__ import annotations
 
+import csv
 import gc
 import json
 import random
@@ -204,10 +211,122 @@ def _record(*, run_id, game_index, game_seed, run_config, seats, scores, winner_
     }
 
 
+# ---------------------------------------------------------------------------- snapshots
+
+SNAPSHOT_META_COLUMNS = ["run_id", "game_id", "game_index", "game_seed", "checkpoint_index", "checkpoint_ply", "ply",
+                         "turn_index", "current_player_id", "player_id", "player_name", "agent_name", "seat_index",
+                         "winner_id", "winner_ids_json", "label_is_winner", "final_score", "final_rank",
+                         "final_scores_json", "is_tie"]
+
+
+def _checkpoint_index(run_config: RunConfig) -> Dict[int, int]:
+    return {ply: i for i, ply in enumerate(sorted(run_config.snapshots.checkpoints))}
+
+
+class SnapshotBatch:
+    """Captured checkpoint positions of any number of games, turned into the reference's
+    snapshot rows (_build_snapshot_rows_for_checkpoint plus the labels of :722-731) by ONE
+    bk_snapshot_features launch per ``flush``."""
+
+    def __init__(self, run_config: RunConfig, device: int = 0):
+        self.run_config = run_config
+        self.device = device
+        self._states: List[np.ndarray] = []
+        self._sets: List[np.ndarray] = []
+        self._meta: List[Dict[str, Any]] = []
+        self._labels: Dict[int, Dict[str, Any]] = {}
+
+    def __len__(self) -> int:
+        return len(self._meta)
+
+    def capture(self, *, run_id: str, game_index: int, game_seed: int, seats: Mapping[str, str], checkpoint_ply: int,
+                state, fset, turn_count: int) -> None:
+        """One position: its bk_state and bk_fset records (copied) and the turn count."""
+        from .. import _native as N
+        st = np.array(state, dtype=N.STATE_DTYPE).reshape(1).copy()
+        self._states.append(st)
+        self._sets.append(np.array(fset, dtype=N.FSET_DTYPE).reshape(1).copy())
+        self._meta.append({"run_id": run_id, "game_index": int(game_index), "game_seed": int(game_seed),
+                           "seats": dict(seats), "checkpoint_index": _checkpoint_index(self.run_config)[checkpoint_ply],
+                           "checkpoint_ply": int(checkpoint_ply), "ply": int(st["move_count"][0]),
+                           "turn_index": int(turn_count), "current_player_id": int(st["current_player"][0]) + 1})
+
+    def label(self, record: Mapping[str, Any]) -> None:
+        """The finished game's record: its rows' label fields, and its checkpoints hit."""
+        self._labels[int(record["game_index"])] = dict(record)
+
+    def checkpoints_hit(self, game_index: int) -> List[int]:
+        return sorted({m["checkpoint_ply"] for m in self._meta if m["game_index"] == game_index})
+
+    def flush(self, rows_out: List[Dict[str, Any]]) -> None:
+        """Append the rows of every capture so far (games in capture order, checkpoints
+        ascending, players in seat order) to rows_out and forget the captures."""
+        from ..analytics.winprob.features import rows_from_launch
+        from ..gpu import BlokusGPU
+        if not self._meta:
+            return
+        order = sorted(range(len(self._meta)), key=lambda i: (self._first_capture(self._meta[i]["game_index"]),
+                                                              self._meta[i]["checkpoint_index"]))
+        states = np.concatenate([self._states[i] for i in order])
+        sets = np.concatenate([self._sets[i] for i in order])
+        turns = np.array([self._meta[i]["turn_index"] for i in order], dtype=np.int32)
+        recs, feats = BlokusGPU.shared(self.device).snapshot_features(states, sets, turns, self.run_config.max_turns)
+        for k, per_player in zip(order, rows_from_launch(recs, feats)):
+            m = self._meta[k]
+            rec = self._labels[m["game_index"]]
+            winner_ids = [int(w) for w in rec["winner_ids"]]
+            for player in Player:
+                pid = int(player.value)
+                row: Dict[str, Any] = {
+                    "run_id": m["run_id"], "game_id": f"{m['run_id']}_g{m['game_index']:04d}",
+                    "game_index": m["game_index"], "game_seed": m["game_seed"],
+                    "checkpoint_index": m["checkpoint_index"], "checkpoint_ply": m["checkpoint_ply"], "ply": m["ply"],
+                    "turn_index": m["turn_index"], "current_player_id": m["current_player_id"], "player_id": pid,
+                    "player_name": player.name, "agent_name": m["seats"][str(pid)], "seat_index": pid - 1,
+                    "winner_id": rec["winner_id"], "winner_ids_json": json.dumps(winner_ids, sort_keys=True),
+                    "label_is_winner": int(pid in winner_ids), "final_score": int(rec["final_scores"][str(pid)]),
+                    "final_rank": int(rec["final_ranks"][str(pid)]),
+                    "final_scores_json": json.dumps(rec["final_scores"], sort_keys=True), "is_tie": bool(rec["is_tie"]),
+                }
+                row.update(per_player[player.name])
+                rows_out.append(row)
+        self._states, self._sets, self._meta, self._labels = [], [], [], {}
+
+    def _first_capture(self, game_index: int) -> int:
+        return next(i for i, m in enumerate(self._meta) if m["game_index"] == game_index)
+
+
+def write_snapshots_csv(run_dir: Path, rows: Sequence[Mapping[str, Any]]) -> Optional[Path]:
+    """snapshots.csv of the rows (metadata columns, then the features, the reference's
+    order); nothing is written, and None returned, when there are no rows."""
+    from ..analytics.winprob.features import SNAPSHOT_FEATURE_COLUMNS
+    if not rows:
+        return None
+    path = Path(run_dir) / "snapshots.csv"
+    with path.open("w", encoding="utf-8", newline="") as fh:
+        w = csv.DictWriter(fh, fieldnames=SNAPSHOT_META_COLUMNS + list(SNAPSHOT_FEATURE_COLUMNS))
+        w.writeheader()
+        for r in rows:
+            w.writerow(r)
+    return path
+
+
 def run_single_game(*, run_id: str, game_index: int, game_seed: int, run_config: RunConfig,
-                    seat_assignment: Mapping[str, str], agent_configs: Mapping[str, AgentConfig]) -> Dict[str, Any]:
+                    seat_assignment: Mapping[str, str], agent_configs: Mapping[str, AgentConfig],
+                    snapshot_rows: Optional[list] = None,
+                    snapshot_batch: Optional[SnapshotBatch] = None) -> Dict[str, Any]:
     """The reference loop (:652-697): pass when stuck, validate every move, game over when
-    nobody can move, max_turns truncation."""
+    nobody can move, max_turns truncation.  With snapshots enabled and ``snapshot_rows``
+    given, the positions at the checkpoints are captured where the reference captures
+    (before the first turn, after every successful move) and their rows appended to
+    snapshot_rows after the game, in one launch; a caller that plays several games passes
+    its own ``snapshot_batch`` instead and flushes it once."""
+    from ..engine.board import pack_state
+    snap = None
+    if run_config.snapshots.enabled and (snapshot_rows is not None or snapshot_batch is not None):
+        snap = snapshot_batch if snapshot_batch is not None else SnapshotBatch(run_config)
+    checkpoints = _checkpoint_index(run_config)
+    hit: set = set()
     random.seed(game_seed)
     np.random.seed(game_seed)
     start = time.perf_counter()
@@ -218,6 +337,17 @@ def run_single_game(*, run_id: str, game_index: int, game_seed: int, run_config:
     game = BlokusGame()
     passes = invalid = turns = 0
     truncated, error = False, None
+
+    def maybe_capture():
+        ply = int(game.board.move_count)
+        if snap is None or ply not in checkpoints or ply in hit:
+            return
+        snap.capture(run_id=run_id, game_index=game_index, game_seed=game_seed, seats=seat_assignment,
+                     checkpoint_ply=ply, state=pack_state(game.board), fset=game.board.frontier_tables,
+                     turn_count=turns)
+        hit.add(ply)
+
+    maybe_capture()  # a checkpoint at ply 0
     try:
         while not game.is_game_over() and turns < run_config.max_turns:
             cur = game.get_current_player()
@@ -244,6 +374,8 @@ def run_single_game(*, run_id: str, game_index: int, game_seed: int, run_config:
                 passes += 1
                 game.board._update_current_player()
                 game._check_game_over()
+                continue
+            maybe_capture()
     except Exception:  # noqa: BLE001 - recorded like the reference
         error = traceback.format_exc()
     if turns >= run_config.max_turns and not game.is_game_over():
@@ -251,11 +383,17 @@ def run_single_game(*, run_id: str, game_index: int, game_seed: int, run_config:
         game.board.game_over = True
     res = game.get_game_result()
     _finish_stats(per_agent)
-    return _record(run_id=run_id, game_index=game_index, game_seed=game_seed, run_config=run_config,
-                   seats=seat_assignment, scores=res.scores, winner_ids=[int(w) for w in res.winner_ids],
-                   is_tie=res.is_tie, moves_made=game.board.move_count, turn_count=turns, passes=passes,
-                   invalid=invalid, duration=time.perf_counter() - start, truncated=truncated,
-                   per_agent=per_agent, error=error)
+    record = _record(run_id=run_id, game_index=game_index, game_seed=game_seed, run_config=run_config,
+                     seats=seat_assignment, scores=res.scores, winner_ids=[int(w) for w in res.winner_ids],
+                     is_tie=res.is_tie, moves_made=game.board.move_count, turn_count=turns, passes=passes,
+                     invalid=invalid, duration=time.perf_counter() - start, truncated=truncated,
+                     per_agent=per_agent, error=error)
+    if snap is not None:
+        record["snapshot_checkpoints_hit"] = sorted(hit)
+        snap.label(record)
+        if snapshot_batch is None:
+            snap.flush(snapshot_rows)
+    return record
 
 
 def _all_random(run_config: RunConfig) -> bool:
@@ -266,10 +404,15 @@ STATUS_CAP = 8  # bk_result.status bit 3 (include/blokus_hip.h)
 
 
 def run_games_gpu(run_config: RunConfig, game_indices: Sequence[int], *, run_id: str = "gpu",
-                  device: int = 0) -> List[Dict[str, Any]]:
+                  device: int = 0, snapshot_rows: Optional[list] = None) -> List[Dict[str, Any]]:
     """All-random seatings: the games ``game_indices`` in one frontier-order playout launch.
     Per-move times are not observable inside the kernel; each game's duration is its
-    share of the launch and per-agent time is split by moves made."""
+    share of the launch and per-agent time is split by moves made.
+    With snapshots enabled and ``snapshot_rows`` given, the games -- deterministic in their
+    seeds -- are replayed from the empty board to every checkpoint c > 0 (SEM_ADVANCE with a
+    budget of c placements: the position, its tables and the turn count at the c-th
+    placement), one bk_snapshot_features launch per checkpoint; a game that ended, or was
+    cut by max_turns, before its c-th placement has no row for c."""
     from .. import _native as N
     from ..gpu import BlokusGPU, empty_state
     if not _all_random(run_config):
@@ -306,6 +449,29 @@ def run_games_gpu(run_config: RunConfig, game_indices: Sequence[int], *, run_id:
         res["turns"][i] -= k
     res["status"] &= ~np.uint8(STATUS_CAP)
     dt = time.perf_counter() - t0
+    snap_on = run_config.snapshots.enabled and snapshot_rows is not None
+    hits: List[List[int]] = [[] for _ in idx]
+    batches: List[SnapshotBatch] = []
+    if snap_on:
+        for c in sorted(run_config.snapshots.checkpoints):
+            if c == 0:
+                st_c, fs_c = np.repeat(empty_state(), n), np.repeat(N.fset_new(1), n)
+                turn_c, reached = np.zeros(n, dtype=np.int64), np.ones(n, dtype=bool)
+            else:
+                st_c, fs_c, res_c = gpu.rollout_frontier(empty_state(), N.fset_new(1), n, semantics=N.SEM_ADVANCE,
+                                                         rng=N.RNG_NUMPY_MT, compat_seeds=seeds, max_plies=c,
+                                                         root_index=np.zeros(n, dtype=np.int32), with_results=True)
+                if (res_c["status"] & ~np.uint8(STATUS_CAP)).any():
+                    raise RuntimeError(f"snapshot replay to ply {c}: kernel status {res_c['status'].max()}")
+                turn_c = res_c["turns"].astype(np.int64)
+                # the c-th placement happened, within the run's turn cap (:653)
+                reached = (st_c["move_count"] == c) & (turn_c <= run_config.max_turns)
+            batch = SnapshotBatch(run_config, device)
+            for i in np.flatnonzero(reached):
+                batch.capture(run_id=run_id, game_index=idx[i], game_seed=gseeds[i], seats=seats[i], checkpoint_ply=c,
+                              state=st_c[i], fset=fs_c[i], turn_count=int(turn_c[i]))
+                hits[i].append(c)
+            batches.append(batch)
     out = []
     for i, gi in enumerate(idx):
         r = res[i]
@@ -328,6 +494,17 @@ def run_games_gpu(run_config: RunConfig, game_indices: Sequence[int], *, run_id:
                            moves_made=int(states[i]["move_count"]), turn_count=turns, passes=int(r["passes"]),
                            invalid=0, duration=dt / n, truncated=bool(alive[i]),
                            per_agent=per_agent, error=None))
+        if snap_on:
+            out[-1]["snapshot_checkpoints_hit"] = hits[i]
+    if snap_on:
+        rows: List[Dict[str, Any]] = []
+        for batch in batches:  # one launch per checkpoint
+            for rec in out:
+                batch.label(rec)
+            batch.flush(rows)
+        pos = {gi: i for i, gi in enumerate(idx)}
+        rows.sort(key=lambda r: (pos[r["game_index"]], r["checkpoint_index"], r["player_id"]))
+        snapshot_rows.extend(rows)
     return out
 
 
@@ -1455,27 +1632,37 @@ def run_experiment(run_config: RunConfig, *, verbose: bool = False, device: int 
     and writes the run (one gather of JSON records, games are independent)."""
     from ..shard import shard_indices
     mine = shard_indices(run_config.num_games, rank, world).tolist()
+    snap_on = run_config.snapshots.enabled
+    snapshot_rows: List[Dict[str, Any]] = []
     if _all_random(run_config):
-        records = run_games_gpu(run_config, mine, run_id="pending", device=device)
-    elif batched and all(_batchable(run_config, seat_assignment_for_game(
+        records = run_games_gpu(run_config, mine, run_id="pending", device=device,
+                                snapshot_rows=snapshot_rows if snap_on else None)
+    elif not snap_on and batched and all(_batchable(run_config, seat_assignment_for_game(
             run_config.agent_names, gi, game_seed_from_run_seed(run_config.seed, gi), run_config.seat_policy))
             for gi in mine):
         records = run_games_batched(run_config, mine, run_id="pending", device=device)
     else:
+        # (with snapshots the batched mixed-agent paths are not used: capture inside
+        # bk_arena_step is a follow-up, DESIGN.md 9)
         agent_configs = {a.name: a for a in run_config.agents}
         records = []
+        batch = SnapshotBatch(run_config, device) if snap_on else None
         for gi in mine:
             gs = game_seed_from_run_seed(run_config.seed, gi)
             seats = seat_assignment_for_game(run_config.agent_names, gi, gs, run_config.seat_policy)
             records.append(run_single_game(run_id="pending", game_index=gi, game_seed=gs, run_config=run_config,
-                                           seat_assignment=seats, agent_configs=agent_configs))
+                                           seat_assignment=seats, agent_configs=agent_configs, snapshot_batch=batch))
             if verbose:
                 print(f"[{gi + 1}/{run_config.num_games}] seed={gs} winners={records[-1]['winner_agents']}")
+        if batch is not None:
+            batch.flush(snapshot_rows)  # one launch for the shard
     if world > 1:
         gathered: List[Any] = [None] * world
-        dist.all_gather_object(gathered, records)
-        records = [r for part in gathered for r in part]
+        dist.all_gather_object(gathered, (records, snapshot_rows))
+        records = [r for part in gathered for r in part[0]]
+        snapshot_rows = [r for part in gathered for r in part[1]]
     records.sort(key=lambda r: r["game_index"])
+    snapshot_rows.sort(key=lambda r: (r["game_index"], r["checkpoint_index"], r["player_id"]))
     if rank != 0:
         return {"run_id": None, "games": len(records)}
     root = Path(run_config.output_root)
@@ -1503,4 +1690,8 @@ def run_experiment(run_config: RunConfig, *, verbose: bool = False, device: int 
                               thinking_time_ms_by_agent={a.name: a.thinking_time_ms for a in run_config.agents},
                               run_config=payload)
     _write_json(run_dir / "summary.json", summary)
+    for row in snapshot_rows:
+        row["run_id"] = run_id
+        row["game_id"] = f"{run_id}_g{row['game_index']:04d}"
+    write_snapshots_csv(run_dir, snapshot_rows)
     return {"run_id": run_id, "run_dir": str(run_dir), "summary": summary}

@@ -7,6 +7,7 @@
 //   analytics/tournament/arena_runner.py:652-697 game loop        (BK_SEM_ARENA)
 //   engine/game.py:182-349            game over / GameResult scoring
 //   engine/telemetry.py:17-198        collect_all_player_metrics (bk_telemetry)
+//   analytics/winprob/features.py:106-192 snapshot feature rows (bk_snapshot_features)
 //
 // Design (DESIGN.md has the full story):
 //   * one lane = one board (one game); 64 games per wave, all control flow uniform
@@ -66,6 +67,7 @@
 #define BK_U_COOP 10
 #define BK_U_COOP_H 11
 #define BK_U_TELEMETRY 12
+#define BK_U_SNAPSHOT 13
 #ifndef BK_TU
 #define BK_TU 0
 #endif
@@ -5697,6 +5699,265 @@ __global__ __launch_bounds__(TEL_WAVES * WAVE) void k_telemetry(TelArgs a) {
 __global__ void k_telemetry(TelArgs a);
 #endif
 
+// ------------------------------------------------------------------------------------
+// Snapshot features: analytics/winprob/features.py:106-192 for batches of boards
+// (bk_snapshot_features).  The mapping is k_telemetry's: one block of four waves per
+// board, wave p working for player p.  Phase A counts the player's legal placements per
+// piece (coop_live_orients / coop_ok_counts / coop_scan) and runs the player's row scans
+// (centre distance, opponent adjacency, cell counts) with board row R in lane R; wave 0
+// also floods the empty cells from every player's frontier keys for the board-wide dead
+// zones.  After the block barrier each wave reads the other three move counts and the
+// dead-zone count from LDS and builds its row: lane i < 21 divides and multiplies for
+// piece i + 1, lanes 0..6 each add one of the seven sums (orientation-normalised, the five
+// size buckets, cell-weighted) in ascending piece id, one rounding per reference operation.
+// No stability run, no shuffle, no MT table.
+// ------------------------------------------------------------------------------------
+#define SNAP_WAVES 4
+struct SnapArgs {
+    const bk_state* states;
+    const bk_fset* sets;
+    const int32_t* turn_index;
+    int32_t n;
+    int32_t max_turns;
+    bk_snapshot_rec* rec;  // n x 4 or null
+    double* feat;          // n x 4 x BK_SNAPSHOT_COLUMNS or null
+};
+
+static_assert(sizeof(bk_snapshot_rec) == 80 && sizeof(bk_snapshot_rec) % 8 == 0, "the record is copied out as dwords");
+static_assert(BK_SNAPSHOT_COLUMNS <= WAVE, "one lane per column");
+
+#if BK_DEF(BK_U_SNAPSHOT)
+// O_i (distinct orientations), S_i (cells) and the pieces of each size, from the orientation table
+struct SnapTab {
+    uint8_t orients[BK_PIECES], size[BK_PIECES];
+    uint32_t of_size[6];  // bit i: piece i + 1 has that many cells
+};
+constexpr uint32_t kSnapInfo[BK_NUM_ORIENTS] = BK_ORIENT_INFO_INIT;
+constexpr SnapTab snap_tab() {
+    SnapTab t{};
+    for (int g = 0; g < BK_NUM_ORIENTS; ++g) {
+        const int i = (int)(kSnapInfo[g] & 0xFFu) - 1;
+        t.orients[i] = (uint8_t)(t.orients[i] + 1);
+        t.size[i] = (uint8_t)((kSnapInfo[g] >> 8) & 0xFFu);
+    }
+    for (int i = 0; i < BK_PIECES; ++i) t.of_size[t.size[i]] |= 1u << i;
+    return t;
+}
+__constant__ SnapTab kSnapTab = snap_tab();
+
+__global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) uint2 s_rows[20 * WAVE];  // column p: player p's {B, C} rows
+    __shared__ uint32_t s_own[4][20], s_occ[20], s_fr[4][20];
+    __shared__ uint32_t s_pc[4][BK_PIECES];  // legal moves per piece
+    __shared__ uint32_t s_mob[4], s_fsz[4], s_dead, s_status;
+    __shared__ int16_t s_otab[SNAP_WAVES][2 * WAVE];
+    __shared__ double s_norm[SNAP_WAVES][BK_PIECES], s_wt[SNAP_WAVES][BK_PIECES];  // P_i / O_i, and that * S_i
+    __shared__ __attribute__((aligned(8))) double s_feat[SNAP_WAVES][BK_SNAPSHOT_COLUMNS];
+    __shared__ __attribute__((aligned(8))) bk_snapshot_rec s_rec[SNAP_WAVES];
+    constexpr int REC_WORDS = (int)(sizeof(bk_snapshot_rec) / 4);
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int p = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const int board = blockIdx.x;  // the grid is exactly n blocks
+    const bk_state* s = a.states + board;
+    const bk_fset* fs = a.sets + board;
+    bk_snapshot_rec& rec = s_rec[p];
+
+    for (int i = tid; i < 4 * 20; i += SNAP_WAVES * WAVE) {
+        (&s_fr[0][0])[i] = 0u;
+        (&s_own[0][0])[i] = plane_row(s->planes[i / 20], i % 20);
+    }
+    for (int i = tid; i < 4 * BK_PIECES; i += SNAP_WAVES * WAVE) (&s_pc[0][0])[i] = 0u;
+    for (int i = tid; i < SNAP_WAVES * REC_WORDS; i += SNAP_WAVES * WAVE) reinterpret_cast<bk_u32_alias*>(s_rec)[i] = 0u;
+    if (tid == 0) s_status = 0u;
+    __syncthreads();
+    if (tid < 20) {
+        const uint32_t o0 = s_own[0][tid], o1 = s_own[1][tid], o2 = s_own[2][tid], o3 = s_own[3][tid];
+        s_occ[tid] = o0 | o1 | o2 | o3;
+        if ((o0 & (o1 | o2 | o3)) | (o1 & (o2 | o3)) | (o2 & o3)) atomicOr(&s_status, BK_SNAP_ST_STATE);
+    }
+    if (lane == 0 && ((s->planes[p][BK_MASK_WORDS - 1] >> (BK_CELLS - 64 * (BK_MASK_WORDS - 1))) || (s->used[p] >> BK_PIECES)))
+        atomicOr(&s_status, BK_SNAP_ST_STATE);
+    // the player's frontier cells as row masks, from the table's keys
+    int tmask = (int)fs->mask[p];
+    bool bad_table = tmask >= BK_FSET_SLOTS;
+    tmask = tmask < BK_FSET_SLOTS ? tmask : BK_FSET_SLOTS - 1;
+    uint32_t fsize = 0;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const int sl = lane + WAVE * h;
+        const int k = sl <= tmask ? (int)fs->key[p][sl] : -1;
+        const bool key = k >= 0 && k < BK_CELLS;
+        bad_table = bad_table || k >= BK_CELLS || k < -2;  // (-1 unused, -2 dummy)
+        if (key) atomicOr(&s_fr[p][k / 20], 1u << (k % 20));
+        fsize += (uint32_t)__popcll(__ballot(key));
+    }
+    if (__ballot(bad_table) && lane == 0) atomicOr(&s_status, BK_SNAP_ST_TABLE);
+    if (lane == 0) s_fsz[p] = fsize;
+    __syncthreads();
+
+    // ---- phase A: legal-move counts per piece
+    const bool first = (s->first_move >> p) & 1u;
+    const uint32_t used = s->used[p] & 0x1FFFFFu;
+    uint2* rows = s_rows + p;
+    {
+        uint32_t own[20], occ[20], B[20], C[20];
+#pragma unroll
+        for (int R = 0; R < 20; ++R) { own[R] = s_own[p][R]; occ[R] = s_occ[R]; }
+        derive_rows(own, occ, first, p, B, C);
+#pragma unroll
+        for (int R = 0; R < 20; ++R) rows[R * WAVE] = make_uint2(B[R], C[R]);
+    }
+    tel_wave_sync();
+    int og[2];
+    const uint32_t nlive = coop_live_orients(~used & 0x1FFFFFu, lane, s_otab[p], og);
+    uint32_t mob;
+    {
+        uint32_t ok0[20], ok1[20], cnt[2];
+        coop_ok_counts(rows, og, nlive, ok0, ok1, cnt);
+        mob = coop_scan(cnt, lane).total;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            if (og[h] >= 0 && cnt[h]) atomicAdd(&s_pc[p][(kInfo[og[h]] & 0xFFu) - 1u], cnt[h]);
+    }
+    // ---- the player's row scans, row R in lane R (the other lanes hold empty rows)
+    const bool rl = lane < 20;
+    const int R = rl ? lane : 0;
+    const uint32_t r_own = rl ? s_own[p][R] : 0u, r_occ = rl ? s_occ[R] : 0u;
+    uint32_t cdist = 9;  // compute_center_proximity: 9 unless a cell is nearer
+    if (r_own) {
+        const uint32_t lo = r_own & 0x3FFu, hi = r_own >> 10;
+        uint32_t dc = 9;
+        if (lo) dc = 9u - (31u - (uint32_t)__builtin_clz(lo));
+        if (hi) { const uint32_t t = (uint32_t)__builtin_ctz(hi); dc = t < dc ? t : dc; }
+        cdist = (uint32_t)(R <= 9 ? 9 - R : R - 10) + dc;
+        cdist = cdist > 9u ? 9u : cdist;
+    }
+#pragma unroll
+    for (int o = WAVE / 2; o; o >>= 1) {
+        const uint32_t t = (uint32_t)__shfl_xor((int)cdist, o);
+        cdist = t < cdist ? t : cdist;
+    }
+    // compute_opponent_adjacency: own cells with another player's cell orthogonally beside them
+    const uint32_t r_opp = r_occ & ~r_own;
+    const uint32_t opp_up = __shfl_up(r_opp, 1), opp_dn = __shfl_down(r_opp, 1);
+    const uint32_t near_opp = (r_opp << 1) | (r_opp >> 1) | (lane >= 1 ? opp_up : 0u) | (lane < WAVE - 1 ? opp_dn : 0u);
+    const uint32_t adj = tel_wave_sum((uint32_t)__builtin_popcount(r_own & near_opp), lane);
+    const uint32_t own_cells = tel_wave_sum((uint32_t)__builtin_popcount(r_own), lane);
+    const uint32_t occ_cells = tel_wave_sum((uint32_t)__builtin_popcount(r_occ), lane);
+    if (p == 0) {
+        // compute_dead_zones: empty cells whose 4-connected component holds no frontier key of any
+        // player = the empty cells a fill from all the keys does not reach (a stale key on an
+        // occupied cell seeds nothing)
+        const uint32_t r_allfr = rl ? (s_fr[0][R] | s_fr[1][R] | s_fr[2][R] | s_fr[3][R]) : 0u;
+        const uint32_t r_empty = rl ? (~r_occ & ROWMASK) : 0u;
+        const uint32_t r_live = tel_flood<1>(r_allfr, r_empty, lane);
+        const uint32_t dead = tel_wave_sum((uint32_t)__builtin_popcount(r_empty & ~r_live), lane);
+        if (lane == 0) s_dead = dead;
+    }
+    if (lane == 0) s_mob[p] = mob;
+    __syncthreads();  // the four move counts, the per-piece counts and the dead-zone count are complete
+
+    // ---- the row
+    const uint32_t dead = s_dead, status = s_status;
+    uint32_t opp_moves = 0, opp_fr = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        opp_moves += q == p ? 0u : s_mob[q];
+        opp_fr += q == p ? 0u : s_fsz[q];
+    }
+    const int corner_diff = (int)fsize - (int)opp_fr;
+    const uint32_t used_count = (uint32_t)__builtin_popcount(used);
+    const int32_t turn = a.turn_index[board];
+    const uint32_t ply = s->move_count;
+    if (lane < BK_PIECES) {
+        const uint32_t P = s_pc[p][lane];
+        rec.piece_count[lane] = (uint16_t)P;
+        const double nrm = __ddiv_rn((double)P, (double)kSnapTab.orients[lane]);  // count / n_orient
+        s_norm[p][lane] = nrm;
+        s_wt[p][lane] = __dmul_rn(nrm, (double)kSnapTab.size[lane]);              // normalized * size
+    }
+    if (lane == 0) {
+        rec.mobility = mob;
+        rec.frontier_size = (uint16_t)fsize;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) rec.frontier_sizes[q] = (uint16_t)s_fsz[q];
+        rec.corner_differential = (int16_t)corner_diff;
+        rec.opponent_adjacency = (uint16_t)adj;
+        rec.deadzone_count = (uint16_t)dead;
+        rec.occupied_cells = (uint16_t)occ_cells;
+        rec.own_cells = (uint16_t)own_cells;
+        rec.center_dist = (uint8_t)cdist;
+        rec.used_count = (uint8_t)used_count;
+        rec.opp_moves_sum = opp_moves;
+        rec.move_count = (uint16_t)ply;
+        rec.status = (uint8_t)status;
+        rec.turn_index = turn;
+    }
+    tel_wave_sync();
+    if (a.rec != nullptr) {
+        bk_u32_alias* dst = reinterpret_cast<bk_u32_alias*>(a.rec + ((size_t)board * 4 + (size_t)p));
+        if (lane < REC_WORDS) dst[lane] = reinterpret_cast<const bk_u32_alias*>(&rec)[lane];
+    }
+    if (a.feat == nullptr) return;  // (uniform)
+    // compute_player_mobility_metrics' sums, pieces in ascending id, used pieces skipped: lane 0
+    // total_norm, lanes 1..5 the size buckets, lane 6 total_weighted
+    double acc = 0.0;
+#pragma unroll 1
+    for (int i = 0; i < BK_PIECES; ++i) {
+        const uint32_t S = kSnapTab.size[i];
+        const double v = lane == 0 ? s_norm[p][i] : s_wt[p][i];
+        const bool take = !((used >> i) & 1u) && (lane == 0 || lane == 6 || (uint32_t)lane == S);
+        acc = take ? __dadd_rn(acc, v) : acc;
+    }
+    double* f = s_feat[p];
+    if (lane == 0) f[7] = acc;
+    if (lane >= 1 && lane <= 5) f[8 + lane] = acc;
+    if (lane == 6) {
+        f[8] = acc;
+        f[15] = __dadd_rn((double)fsize, acc);  // frontier_size + totalCellWeighted
+    }
+    if (lane == 0) {
+        const uint32_t avail = ~used & 0x1FFFFFu;
+        const double cells = (double)BK_CELLS;
+        const double span = (double)(a.max_turns > 1 ? a.max_turns : 1);  // max(1, max_turns)
+        uint32_t squares = 0;
+#pragma unroll
+        for (int b = 1; b <= 5; ++b) {
+            const uint32_t nb = (uint32_t)__builtin_popcount(avail & kSnapTab.of_size[b]);
+            f[18 + b] = (double)nb;  // remaining_size_b_count
+            squares += (uint32_t)b * nb;
+        }
+        f[0] = (double)fsize;
+        f[1] = (double)corner_diff;
+        f[2] = (double)cdist;
+        f[3] = (double)adj;
+        f[4] = (double)dead;
+        f[5] = __ddiv_rn((double)dead, cells);
+        f[6] = (double)mob;
+        f[14] = (double)opp_moves;
+        f[16] = (double)used_count;
+        f[17] = (double)(BK_PIECES - used_count);
+        f[18] = (double)squares;  // total squares - used squares
+        f[24] = (double)((avail >> 16) & 1u);
+        f[25] = (double)((avail >> 18) & 1u);
+        f[26] = (double)((avail >> 19) & 1u);
+        f[27] = (double)ply;
+        f[28] = (double)turn;
+        f[29] = __ddiv_rn((double)occ_cells, cells);
+        f[30] = __ddiv_rn((double)used_count, 21.0);
+        f[31] = __ddiv_rn((double)turn, span);
+        f[32] = __ddiv_rn((double)ply, span);
+        f[33] = __ddiv_rn((double)own_cells, cells);
+    }
+    tel_wave_sync();
+    if (lane < BK_SNAPSHOT_COLUMNS)
+        a.feat[((size_t)board * 4 + (size_t)p) * BK_SNAPSHOT_COLUMNS + (size_t)lane] = f[lane];
+}
+#else
+__global__ void k_snapshot(SnapArgs a);
+#endif
+
 #if BK_DEF(BK_U_HOST)
 // ------------------------------------------------------------------------------------
 // C ABI
@@ -6554,6 +6815,52 @@ int bk_telemetry(bk_handle h, const bk_state* states, const bk_fset* sets, int32
     HIPCHK(h, mark_end(h));
     if (mem == BK_MEM_HOST) {
         HIPCHK(h, hipMemcpyAsync(out, d_outp, out_bytes, hipMemcpyDeviceToHost, h->cur));
+        HIPCHK(h, hipStreamSynchronize(h->cur));
+    }
+    return BK_OK;
+}
+
+int bk_snapshot_rec_size(void) { return (int)sizeof(bk_snapshot_rec); }
+
+int bk_snapshot_features(bk_handle h, const bk_state* states, const bk_fset* sets, int32_t n, const int32_t* turn_index,
+                         int32_t max_turns, bk_snapshot_rec* rec, double* features, int mem) {
+    if (!h || !states || !sets || !turn_index || n < 0 || (mem != BK_MEM_HOST && mem != BK_MEM_DEVICE))
+        return set_err(h, BK_EINVAL, "bk_snapshot_features: invalid arguments%s", "");
+    if (!rec && !features) return set_err(h, BK_EINVAL, "bk_snapshot_features: rec and features are both NULL%s", "");
+    if (max_turns < 0) return set_err(h, BK_EINVAL, "bk_snapshot_features: max_turns must be >= 0%s", "");
+    if (mem == BK_MEM_DEVICE && (((uintptr_t)sets & 15) || ((uintptr_t)states & 7) || ((uintptr_t)rec & 7) ||
+                                 ((uintptr_t)features & 7) || ((uintptr_t)turn_index & 3)))
+        return set_err(h, BK_EINVAL, "bk_snapshot_features: sets must be 16-byte, states, rec and features 8-byte, "
+                                     "turn_index 4-byte aligned%s", "");
+    if (n == 0) return BK_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    BK_IDLE(h, "bk_snapshot_features");
+    void *d_states, *d_sets, *d_turn;
+    int rc = stage_in(h, states, sizeof(bk_state) * (size_t)n, mem, &d_states, &h->d_in, &h->d_in_cap);
+    if (rc) return rc;
+    rc = stage_in(h, sets, sizeof(bk_fset) * (size_t)n, mem, &d_sets, &h->d_fin, &h->d_fin_cap);
+    if (rc) return rc;
+    rc = stage_in(h, turn_index, sizeof(int32_t) * (size_t)n, mem, &d_turn, &h->d_aux, &h->d_aux_cap);
+    if (rc) return rc;
+    const size_t rec_bytes = sizeof(bk_snapshot_rec) * 4 * (size_t)n;
+    const size_t feat_bytes = sizeof(double) * BK_SNAPSHOT_COLUMNS * 4 * (size_t)n;
+    bk_snapshot_rec* d_rec = rec;
+    double* d_feat = features;
+    if (mem == BK_MEM_HOST) {  // one staging buffer: the records, then the rows (rec_bytes is a multiple of 8)
+        rc = grow(h, &h->d_out, &h->d_out_cap, rec_bytes + feat_bytes);
+        if (rc) return rc;
+        d_rec = rec ? (bk_snapshot_rec*)h->d_out : nullptr;
+        d_feat = features ? (double*)((char*)h->d_out + rec_bytes) : nullptr;
+    }
+    SnapArgs a{(const bk_state*)d_states, (const bk_fset*)d_sets, (const int32_t*)d_turn, n, max_turns, d_rec, d_feat};
+    HIPCHK(h, mark_start(h));
+    h->last_kernel = "k_snapshot";
+    hipLaunchKernelGGL(k_snapshot, dim3(n), dim3(SNAP_WAVES * WAVE), 0, h->cur, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, mark_end(h));
+    if (mem == BK_MEM_HOST) {
+        if (rec) HIPCHK(h, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, h->cur));
+        if (features) HIPCHK(h, hipMemcpyAsync(features, d_feat, feat_bytes, hipMemcpyDeviceToHost, h->cur));
         HIPCHK(h, hipStreamSynchronize(h->cur));
     }
     return BK_OK;

@@ -183,6 +183,46 @@ class BlokusGPU:
         self.handle.telemetry(st.ctypes.data, fs.ctypes.data, n, cfg, out.ctypes.data, N.MEM_HOST)
         return out
 
+    def snapshot_features(self, states, sets, turn_index, max_turns: int, *, records: bool = True,
+                          features: bool = True):
+        """The win-probability snapshot rows of n boards, four players each, in one launch
+        (bk_snapshot_features): states and sets as telemetry, turn_index int32[n] (the arena's
+        turn count at each capture), max_turns the run's.  Returns (records, features):
+        records [n, 4] of N.SNAPSHOT_REC_DTYPE, features float64 [n, 4, 34] in
+        SNAPSHOT_FEATURE_COLUMNS order (None for the one not asked for).  Torch cuda in gives
+        torch out: records a uint8 cuda tensor [n, 4, 80], features a float64 cuda tensor."""
+        if not (records or features):
+            raise ValueError("snapshot_features: ask for records, features or both")
+        item = N.SNAPSHOT_REC_DTYPE.itemsize
+        if _is_torch(states):
+            import torch
+            n = states.shape[0]
+            _check_device_tensor(states, "states", torch.uint8, (n, 256), self.device)
+            _check_device_tensor(sets, "sets", torch.uint8, (n, N.FSET_DTYPE.itemsize), self.device)
+            _check_device_tensor(turn_index, "turn_index", torch.int32, (n,), self.device)
+            rec = torch.empty((n, 4, item), dtype=torch.uint8, device=states.device) if records else None
+            feat = (torch.empty((n, 4, N.SNAPSHOT_COLUMNS), dtype=torch.float64, device=states.device)
+                    if features else None)
+            self._stream_from_torch()
+            self.handle.snapshot_features(states.data_ptr(), sets.data_ptr(), n, turn_index.data_ptr(), max_turns,
+                                          rec.data_ptr() if records else 0, feat.data_ptr() if features else 0,
+                                          N.MEM_DEVICE)
+            return rec, feat
+        st = np.ascontiguousarray(states).view(np.uint8)
+        fs = np.ascontiguousarray(sets).view(np.uint8)
+        n = st.size // 256
+        st, fs = st.reshape(n, 256), fs.reshape(n, N.FSET_DTYPE.itemsize)
+        ti = np.ascontiguousarray(turn_index, dtype=np.int32).reshape(-1)
+        if ti.shape[0] != n:
+            raise ValueError(f"turn_index: {ti.shape[0]} entries for {n} boards")
+        rec = np.zeros((n, 4), dtype=N.SNAPSHOT_REC_DTYPE) if records else None
+        feat = np.zeros((n, 4, N.SNAPSHOT_COLUMNS), dtype=np.float64) if features else None
+        self.handle.set_stream(None)
+        self.handle.snapshot_features(st.ctypes.data, fs.ctypes.data, n, ti.ctypes.data, max_turns,
+                                      rec.ctypes.data if records else 0, feat.ctypes.data if features else 0,
+                                      N.MEM_HOST)
+        return rec, feat
+
     def has_moves(self, states):
         """uint8 mask per state: bit p set iff player p has a legal move (move_generator.py:961)."""
         if _is_torch(states):

@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""bk_snapshot_features throughput: the win-probability snapshot rows (four players, 34
+columns) of a batch of mid-game boards in one launch.
+
+Positions: --boards (default 4,096) boards spread evenly over plies --min-ply..--max-ply
+(default 8..40), played from the empty board on the GPU (bk_rollout_frontier,
+BK_SEM_ADVANCE) so each comes with its frontier tables -- the batch tools/telemetry_bench.py
+times.  After --warmup launches the same batch is launched --launches times (>= 10) from
+device tensors, records and feature matrix both written; each launch is timed by the
+library's HIP events around k_snapshot (bk_last_kernel_ms).  One JSON line: boards/s from
+the median launch, and the spread (min / max / relative half-range).  --with-telemetry
+also times bk_telemetry (stability on, k = 3) on the same tensors in the same process,
+the launches of the two kernels alternating.
+
+The comparison point is the reference's build_snapshot_runtime_context +
+extract_player_snapshot_features for the four players on one CPU core over the same ply
+range (profiles/winprob/README.md has the measured pair); this tool never compares
+against the code under test.  --cpu-reference PATH times the reference checkout at PATH
+on this machine's CPU instead (no GPU call; positions from generate_random_valid_state
+over the same plies).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def cpu_reference(path: str, calls: int, lo: int, hi: int) -> dict:
+    sys.path.insert(0, path)
+    from analytics.winprob.features import build_snapshot_runtime_context, extract_player_snapshot_features
+    from engine.board import Player
+    from engine.move_generator import LegalMoveGenerator
+    from tests.utils_game_states import generate_random_valid_state
+    mg = LegalMoveGenerator()
+    times = []
+    for i in range(calls):
+        ply = lo + (i * (hi - lo)) // max(1, calls - 1)
+        board, _ = generate_random_valid_state(ply, 1000 + i)
+        t0 = time.perf_counter()
+        ctx = build_snapshot_runtime_context(board, turn_index=ply, max_turns=2500)
+        for p in Player:
+            extract_player_snapshot_features(board, player=p, context=ctx, move_generator=mg)
+        times.append(time.perf_counter() - t0)
+    return {"tool": "winprob_bench", "what": "reference snapshot rows of one board (context + 4 players), one CPU core",
+            "calls": calls, "min_ply": lo, "max_ply": hi, "boards_per_s": calls / sum(times),
+            "median_s": statistics.median(times), "min_s": min(times), "max_s": max(times)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--boards", type=int, default=4096)
+    ap.add_argument("--min-ply", type=int, default=8)
+    ap.add_argument("--max-ply", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--seed", type=int, default=11)
+    ap.add_argument("--with-telemetry", action="store_true", help="also time bk_telemetry on the same boards")
+    ap.add_argument("--cpu-reference", metavar="PATH", help="time the reference checkout at PATH on the CPU instead")
+    ap.add_argument("--cpu-calls", type=int, default=33)
+    args = ap.parse_args()
+    if args.cpu_reference:
+        print(json.dumps(cpu_reference(args.cpu_reference, args.cpu_calls, args.min_ply, args.max_ply)), flush=True)
+        return
+    if args.launches < 10:
+        ap.error("--launches must be at least 10")
+    import torch
+
+    from reinforcementlearning_blokus_amd import _native as N
+    from reinforcementlearning_blokus_amd.gpu import BlokusGPU, empty_state
+    gpu = BlokusGPU(0)
+    plies = list(range(args.min_ply, args.max_ply + 1))
+    per = [args.boards // len(plies) + (1 if i < args.boards % len(plies) else 0) for i in range(len(plies))]
+    states, sets = [], []
+    for ply, cnt in zip(plies, per):
+        if cnt == 0:
+            continue
+        st, fs = gpu.rollout_frontier(empty_state(), N.fset_new(1), cnt, semantics=N.SEM_ADVANCE, rng=N.RNG_PHILOX,
+                                      seed=args.seed + ply, max_plies=ply, root_index=np.zeros(cnt, dtype=np.int32))
+        states.append(st)
+        sets.append(fs)
+    states, sets = np.concatenate(states), np.concatenate(sets)
+    n = len(states)
+    dev = torch.device("cuda", 0)
+    d_st = torch.from_numpy(states.view(np.uint8).reshape(n, 256).copy()).to(dev)
+    d_fs = torch.from_numpy(sets.view(np.uint8).reshape(n, N.FSET_DTYPE.itemsize).copy()).to(dev)
+    d_ti = torch.from_numpy(states["move_count"].astype(np.int32)).to(dev)
+    ms, tel_ms = [], []
+    for i in range(args.warmup + args.launches):
+        rec, feat = gpu.snapshot_features(d_st, d_fs, d_ti, 2500)
+        gpu.synchronize()
+        if i >= args.warmup:
+            ms.append(gpu.last_kernel_ms())
+        if args.with_telemetry:
+            gpu.telemetry(d_st, d_fs, k_samples=3)
+            gpu.synchronize()
+            if i >= args.warmup:
+                tel_ms.append(gpu.last_kernel_ms())
+    rec = rec.cpu().numpy().view(N.SNAPSHOT_REC_DTYPE).reshape(n, 4)
+    feat = feat.cpu().numpy()
+    med = statistics.median(ms)
+    out = {
+        "tool": "winprob_bench", "kernel": "k_snapshot", "boards": n, "min_ply": args.min_ply,
+        "max_ply": args.max_ply, "warmup": args.warmup, "launches": len(ms),
+        "kernel_ms_median": med, "kernel_ms_min": min(ms), "kernel_ms_max": max(ms),
+        "spread_rel": (max(ms) - min(ms)) / (2 * med), "boards_per_s": n / (med * 1e-3),
+        "rows_per_s": 4 * n / (med * 1e-3), "move_generations_per_s": 4 * n / (med * 1e-3),
+        "status_nonzero": int((rec["status"] != 0).sum()), "mean_mobility": float(rec["mobility"].mean()),
+        "mean_deadzone_count": float(rec["deadzone_count"].mean()),
+        "features_finite": bool(np.isfinite(feat).all()),
+    }
+    if tel_ms:
+        tmed = statistics.median(tel_ms)
+        out.update(telemetry_ms_median=tmed, telemetry_ms_min=min(tel_ms), telemetry_ms_max=max(tel_ms),
+                   snapshot_over_telemetry=med / tmed)
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
