@@ -1642,7 +1642,7 @@ __host__ __device__ inline bool fs_resize(FsetRef t, int16_t* tmp, uint32_t minu
 // per step from the pair-stored tables measured slower (frontier-order config 3 34.1 ->
 // 33.2 / 33.0 M playouts/s, config 5 17.6 -> 17.1 / 17.0 M; profiles/r05/sweeps/r05f):
 // most chains end at their first or second slot.
-// t.gchunk (a table probed in global memory, k_rollout_fr's 128-slot tables): the probe
+// t.gchunk (a table probed in global memory, k_rollout_fr_h's 256-slot tables): the probe
 // reads the 16-byte chunk holding slot e (8 slots, one memory latency) and walks the
 // linear run from registers, loading the next chunk only when the sequence leaves it.
 __host__ __device__ inline void fs_probe(FsetRef t, int16_t k, uint64_t h, uint32_t mask, uint32_t& e_out,
@@ -2052,10 +2052,168 @@ __device__ __forceinline__ bool place_frontier(FsLane* fl, int p, int16_t* lk, c
     // (a table too large for the stage: its resizes use the lane's whole column of the
     // area, STAGE keys, as their scratch -- the stage is not in use)
     FsetRef gt{gfs->key[p], 2, hm, hf, hu, BK_FSET_SLOTS, htab};
-    gt.gchunk = ltk != nullptr;  // (the playout kernels: k_rollout_fr)
+    gt.gchunk = ltk != nullptr;  // (k_rollout_fr_h; k_rollout_fr runs place_frontier_onepass)
     if (!fs_run_ops(gt, fl->tmp, cells, real, lds_tmp(ltk ? lk : nullptr, (uint32_t)STAGE))) return false;
     if constexpr (RECOPY) return fs_recopy_global(fl, p, htab);  // (MCTS records: hdr is nullptr)
     return true;
+}
+
+// ---- k_rollout_fr: the staged and the in-place tables of a wave in ONE op loop ----------
+// place_frontier runs fs_run_ops twice per ply when a wave holds both kinds of movers
+// (almost always: ~12 % of movers have a table of >= STAGE slots): once for the lanes
+// staged in LDS, once more for the few lanes whose table stays in global memory, and a
+// wave pays for each divergent loop by its busiest lane.  Here every lane keeps its table
+// where place_frontier would (its LDS column, stride 2 * WAVE, dirty-chunk tracking; or
+// the global table, stride 2, capacity BK_FSET_SLOTS) and one loop serves both, so the
+// trip count per ply is max-ops(all lanes) instead of max-ops(staged) + max-ops(in
+// place).  The table is addressed through a generic pointer per lane, so one flat load or
+// store serves both kinds, in the probes and in the resizes: 42.4 M playouts/s against
+// 41.4 M with a per-lane branch at each access (ds_read / ds_write on one side, 8-slot
+// chunk probes of the global table on the other) and 40.7 M for the two loops
+// (profiles/r08/sweeps/r08a).  The header (mask, fill, used) lives in registers for both
+// kinds and goes back to memory once, where it changed.
+struct FsMix {
+    int16_t* lk;     // this lane's LDS column (the stage; scratch when the table is in place)
+    int16_t* gk;     // the table in global memory
+    bool glob;       // the ops run on gk (a table of >= STAGE slots, or one that outgrew the stage)
+    uint16_t m, f, u;
+    uint32_t dirty;  // staged: 8-slot chunks the ops wrote (all: a resize)
+    __device__ __forceinline__ int16_t* slot(uint32_t e) const {
+        return (glob ? gk : lk) + ((e >> 1) * (glob ? 2u : 2u * WAVE) + (e & 1u));
+    }
+    __device__ __forceinline__ void put(uint32_t e, int16_t v) {
+        *slot(e) = v;
+        dirty |= 1u << ((e >> 3) & 31u);
+    }
+};
+
+// fs_op_nr (fs_probe's sequence) on a lane's own kind of table
+__device__ __forceinline__ bool fs_op_mix(FsMix& t, int16_t k, bool add, uint64_t h) {
+    const uint32_t mask = t.m;
+    uint64_t perturb = h;
+    uint32_t i = (uint32_t)h & mask, e = i;
+    uint32_t left = i + FS_PROBES <= mask ? FS_PROBES : 0u;
+    int32_t freeslot = -1;
+    int16_t kk;
+    for (;;) {
+        kk = *t.slot(e);
+        if (kk == FS_UNUSED || kk == k) break;
+        if (kk == FS_DUMMY) freeslot = (int32_t)e;
+        if (left > 0u) {
+            --left;
+            ++e;
+        } else {
+            perturb >>= FS_SHIFT;
+            i = (i * 5u + 1u + (uint32_t)perturb) & mask;
+            e = i;
+            left = i + FS_PROBES <= mask ? FS_PROBES : 0u;
+        }
+    }
+    if (kk == k) {  // present: discard leaves a dummy, add is a no-op
+        if (!add) {
+            t.put(e, FS_DUMMY);
+            t.u -= 1;
+        }
+        return false;
+    }
+    if (!add) return false;
+    if (freeslot >= 0) {
+        t.u += 1;
+        t.put((uint32_t)freeslot, k);
+        return false;
+    }
+    t.f += 1;
+    t.u += 1;
+    t.put(e, k);
+    return (uint64_t)t.f * 5 >= (uint64_t)mask * 3;
+}
+
+// fs_run_ops<true> for a wave of both kinds.  A staged lane whose table outgrows the stage
+// switches to its global table, which the stage never wrote to: it takes back the header
+// it loaded and all of its ops and goes on in the same loop (its column, no longer a
+// stage, becomes its resize scratch).  false: the 256-slot storage overflowed.
+template <int STAGE>
+__device__ __forceinline__ bool fs_run_ops_mix(FsMix& t, int16_t* tmp, int16_t* ltk, const uint64_t* htab,
+                                               const int32_t (&cells)[5], uint64_t real) {
+    constexpr uint64_t KD = (21ull << 0) | (0ull << 6) | (2ull << 12) | (40ull << 18) | (42ull << 24) |
+                            (1ull << 30) | (41ull << 36) | (20ull << 42) | (22ull << 48);  // fs_run_ops
+    const uint64_t real0 = real;
+    const uint16_t m0 = t.m, f0 = t.f, u0 = t.u;
+    bool ok = true;
+#pragma unroll 1
+    for (;;) {
+        bool need = false;
+#pragma unroll 1
+        while (real && !need) {
+            const int s = (int)__builtin_ctzll(real);
+            real &= real - 1ull;
+            const int q = (s * 57) >> 9;  // s / 9 for s < 45
+            const int op = s - 9 * q;
+            const int cell = q == 0 ? cells[0] : q == 1 ? cells[1] : q == 2 ? cells[2] : q == 3 ? cells[3] : cells[4];
+            const int key = cell + (int)((KD >> (6 * op)) & 63ull) - 21;
+            need = fs_op_mix(t, (int16_t)key, (unsigned)(op - 1) < 4u, htab[key]);
+        }
+        if (need) {  // the resizes of a round run together (fs_run_ops), each lane with its own scratch
+            FsetRef r{t.glob ? t.gk : t.lk, t.glob ? 2 : 2 * WAVE, &t.m, &t.f, &t.u,
+                      t.glob ? (uint32_t)BK_FSET_SLOTS : (uint32_t)STAGE, htab, 1, &t.dirty};
+            if (!fs_resize_any(r, tmp, lds_tmp(t.glob ? t.lk : ltk, t.glob ? (uint32_t)STAGE : STAGE / 4))) {
+                if (t.glob) {
+                    ok = false;
+                    real = 0;
+                } else {
+                    t.glob = true;
+                    t.m = m0; t.f = f0; t.u = u0;
+                    real = real0;
+                }
+            }
+        }
+        if (__builtin_amdgcn_ballot_w64(real != 0ull) == 0ull) break;
+    }
+    return ok;
+}
+
+// place_frontier<STAGE> for k_rollout_fr (hdr and ltk set, no RECOPY): stage, one op loop
+// for every lane, write-back of the staged lanes' dirty chunks
+template <int STAGE, typename Mark>
+__device__ __forceinline__ bool place_frontier_onepass(FsLane* fl, int p, int16_t* lk, const uint64_t* htab,
+                                                       const int32_t (&cells)[5], uint64_t real, Mark mark,
+                                                       uint16_t* hdr, int16_t* ltk) {
+    static_assert(STAGE > 0 && STAGE <= STAGE_EAGER_MAX && STAGE <= 256, "an eager stage; dirty holds 32 chunks");
+    bk_fset* gfs = &fl->s;
+    const bk_u4_alias* src4 = reinterpret_cast<const bk_u4_alias*>(gfs->key[p]);
+    uint4 pre[STAGE / 8];  // (the eager stage load of place_frontier)
+#pragma unroll
+    for (int i = 0; i < STAGE / 8; ++i) pre[i] = src4[i];
+    const uint16_t m0 = hdr[0], f0 = hdr[1], u0 = hdr[2];
+    bk_u32_alias* lw = reinterpret_cast<bk_u32_alias*>(lk);
+    FsMix t{lk, gfs->key[p], m0 >= (uint16_t)STAGE, m0, f0, u0, 0u};
+    if (!t.glob) {
+#pragma unroll
+        for (int i = 0; i < STAGE / 8; ++i) {
+            if ((uint32_t)(8 * i) <= (uint32_t)m0) {
+                lw[(4 * i + 0) * WAVE] = pre[i].x;
+                lw[(4 * i + 1) * WAVE] = pre[i].y;
+                lw[(4 * i + 2) * WAVE] = pre[i].z;
+                lw[(4 * i + 3) * WAVE] = pre[i].w;
+            }
+        }
+    }
+    mark(8);
+    const bool ok = fs_run_ops_mix<STAGE>(t, fl->tmp, ltk, htab, cells, real);
+    mark(9);
+    if (!t.glob) {
+        bk_u4_alias* dst4 = reinterpret_cast<bk_u4_alias*>(gfs->key[p]);
+#pragma unroll
+        for (int i = 0; i < STAGE / 8; ++i) {
+            if ((uint32_t)(8 * i) <= (uint32_t)t.m && ((t.dirty >> i) & 1u))
+                dst4[i] = make_uint4(lw[(4 * i + 0) * WAVE], lw[(4 * i + 1) * WAVE], lw[(4 * i + 2) * WAVE],
+                                     lw[(4 * i + 3) * WAVE]);
+        }
+    }
+    if (t.m != m0) hdr[0] = t.m;
+    if (t.f != f0) hdr[1] = t.f;
+    if (t.u != u0) hdr[2] = t.u;
+    return ok;
 }
 
 // k_mcts_pair's LDS-DMA stage of the mover's table: the lane pair (2q, 2q + 1) loads run
@@ -3191,9 +3349,14 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a) {
             // resize scratch: the area's dwords after the stage (FR: 32..39, HEUR: 64..83)
             constexpr int STG = HEUR ? 128 : BK_FS_STAGE_FR;
             static_assert(STG / 2 + STG / 8 <= AREA / WAVE, "the resize scratch fits the area");
-            if (!place_frontier<STG>(&a.fslab[slot], p, lk, htab, cells, real, mark, slab_hdr(slab, p),
-                                     lk + 2 * WAVE * (STG / 2)))
-                g.status |= 2u;
+            bool placed;
+            if constexpr (HEUR)
+                placed = place_frontier<STG>(&a.fslab[slot], p, lk, htab, cells, real, mark, slab_hdr(slab, p),
+                                             lk + 2 * WAVE * (STG / 2));
+            else  // k_rollout_fr: one op loop for the staged and the in-place tables of the wave
+                placed = place_frontier_onepass<STG>(&a.fslab[slot], p, lk, htab, cells, real, mark,
+                                                     slab_hdr(slab, p), lk + 2 * WAVE * (STG / 2));
+            if (!placed) g.status |= 2u;
         }
         SECT(6);
         g.cells.set(p, g.cells.get(p) + (uint32_t)n);
