@@ -687,9 +687,12 @@ __device__ __forceinline__ void locate_pass1(int gs, uint2* rows) {
 
 // RS: uint4 distance between 16-slot runs of the table (2: a plain array; 64: the lane
 // pair's LDS-DMA stage of k_mcts_pair)
-template <int RS = 2>
+// LIVE (k_rollout_fr): lmv is the stored mask of the live slots of a table of <= 128
+// slots (live_masks), and the pass that rebuilds it from the slots is left out
+template <int RS = 2, bool LIVE = false>
 __device__ __forceinline__ void locate_move_frontier(const OrientRow& orow, uint32_t kk, uint2* rows,
-                                                     const int16_t* key, int mask, int& out_r, int& out_c) {
+                                                     const int16_t* key, int mask, int& out_r, int& out_c,
+                                                     uint4 lmv = uint4{}) {
     const uint32_t info = orow.info;
     const int n = (int)((info >> 8) & 0xFFu);
     const int rlim = 20 - (int)((info >> 16) & 0xFFu);
@@ -794,7 +797,9 @@ __device__ __forceinline__ void locate_move_frontier(const OrientRow& orow, uint
         // lm[0] bit 0 is the lowest slot not yet taken, slot lbase: a drained word is
         // shifted out, so the next slot always comes from lm[0] (all indices static).
         uint32_t lm[4] = {0u, 0u, 0u, 0u};
-        {
+        if constexpr (LIVE) {
+            lm[0] = lmv.x; lm[1] = lmv.y; lm[2] = lmv.z; lm[3] = lmv.w;
+        } else {
             uint4 qa = k4[0], qb = k4[1];  // tables hold >= 8 slots; the storage has 256
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
@@ -1573,7 +1578,7 @@ __host__ __device__ __forceinline__ uint32_t fs_clean_slot(uint64_t h, uint32_t 
 // global memory and re-inserts one dependent memory latency at a time: resizes were ~86 %
 // of k_rollout_fr's set-operation time and ~90 % of k_mcts_pair's
 // (profiles/r05/sweeps/r05n, -DBK_SECTION_PROF).
-__host__ __device__ inline bool fs_resize_lds(FsetRef t, FsetRef tmp, uint32_t minused) {
+__host__ __device__ inline bool fs_resize_lds(FsetRef t, FsetRef tmp, uint32_t minused, SlotBits* occ = nullptr) {
     uint32_t newsize = 8;
     while (newsize <= minused) newsize <<= 1;
     if (newsize > t.cap) return false;
@@ -1606,6 +1611,7 @@ __host__ __device__ inline bool fs_resize_lds(FsetRef t, FsetRef tmp, uint32_t m
         for (int q = 0; q < 8; ++q)
             if (k[q] >= 0) t.at(fs_clean_slot(h[q], newsize - 1u, o)) = k[q];
     }
+    if (occ) *occ = o;  // the new table's used slots (k_rollout_fr: its live mask)
     return true;
 }
 
@@ -2078,12 +2084,34 @@ struct FsMix {
     bool glob;       // the ops run on gk (a table of >= STAGE slots, or one that outgrew the stage)
     uint16_t m, f, u;
     uint32_t dirty;  // staged: 8-slot chunks the ops wrote (all: a resize)
+    // The table's live slots (bit s & 31 of word s / 32: key[s] >= 0) while it has <= 128
+    // slots, carried from ply to ply next to the game (live_masks; not meaningful for a
+    // larger table).  During the ops the four words sit in LDS, in dwords lmw[w * WAVE] of the
+    // lane's column behind the stage (the first half of the staged lanes' resize scratch,
+    // which fs_resize_mix reads out before it uses the scratch).  Every put of fs_op_mix
+    // flips its slot between live and dead (a key becomes a dummy; a dummy or an unused
+    // slot takes a key), so a put is one ds_xor: no register is held across the probe
+    // loop and the update costs the VALU an address and a shift.  (The four words in
+    // registers, updated with selects, cost 3.7 %: profiles/r09/sweeps/r09a.)  Slots
+    // >= 128 of a 256-slot table flip bits of the four dwords after them, which nobody
+    // reads.
+    bk_u32_alias* lmw;
     __device__ __forceinline__ int16_t* slot(uint32_t e) const {
         return (glob ? gk : lk) + ((e >> 1) * (glob ? 2u : 2u * WAVE) + (e & 1u));
     }
     __device__ __forceinline__ void put(uint32_t e, int16_t v) {
         *slot(e) = v;
         dirty |= 1u << ((e >> 3) & 31u);
+        __hip_atomic_fetch_xor(lmw + (e >> 5) * WAVE, 1u << (e & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+    __device__ __forceinline__ uint4 live_mask() const {
+        return make_uint4(lmw[0], lmw[WAVE], lmw[2 * WAVE], lmw[3 * WAVE]);
+    }
+    __device__ __forceinline__ void set_live_mask(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+        lmw[0] = a;
+        lmw[WAVE] = b;
+        lmw[2 * WAVE] = c;
+        lmw[3 * WAVE] = d;
     }
 };
 
@@ -2128,13 +2156,35 @@ __device__ __forceinline__ bool fs_op_mix(FsMix& t, int16_t k, bool add, uint64_
     return (uint64_t)t.f * 5 >= (uint64_t)mask * 3;
 }
 
+// set_table_resize after an add reached the threshold (fs_resize_any) on a lane's own kind
+// of table: fs_resize_lds, whose occupancy bitmap of the new table becomes the live mask.
+// The scratch is the lane's LDS column (in place: the unused stage, STAGE keys; staged:
+// ltk, STAGE / 4 keys, which overwrite the old mask): a resize that fits the storage has
+// used * 4 < newsize <= cap, so the active keys always fit it and fs_resize_any's fallback
+// through the record's tmp is never taken.  false: the storage cannot hold the new table
+// (nothing written).  (Gathering the old table's keys by the live mask, two loads per
+// trip, instead of the scan of every slot measured +0.2 %, inside the run-to-run spread:
+// left out, profiles/r09/sweeps/r09a.)
+template <int STAGE>
+__device__ __forceinline__ bool fs_resize_mix(FsMix& t, int16_t* ltk, const uint64_t* htab) {
+    static_assert(STAGE * 4 >= BK_FSET_SLOTS, "the in-place lanes' scratch (STAGE keys) holds cap / 4 keys");
+    FsetRef r{t.glob ? t.gk : t.lk, t.glob ? 2 : 2 * WAVE, &t.m, &t.f, &t.u,
+              t.glob ? (uint32_t)BK_FSET_SLOTS : (uint32_t)STAGE, htab, 1};
+    SlotBits o;
+    if (!fs_resize_lds(r, lds_tmp(t.glob ? t.lk : ltk, t.glob ? (uint32_t)STAGE : STAGE / 4), (uint32_t)t.u * 4u, &o))
+        return false;
+    t.dirty = ~0u;  // every slot is rewritten
+    t.set_live_mask((uint32_t)o.w0, (uint32_t)(o.w0 >> 32), (uint32_t)o.w1, (uint32_t)(o.w1 >> 32));
+    return true;
+}
+
 // fs_run_ops<true> for a wave of both kinds.  A staged lane whose table outgrows the stage
 // switches to its global table, which the stage never wrote to: it takes back the header
-// it loaded and all of its ops and goes on in the same loop (its column, no longer a
-// stage, becomes its resize scratch).  false: the 256-slot storage overflowed.
+// and the live mask it loaded and all of its ops and goes on in the same loop (its column,
+// no longer a stage, becomes its resize scratch).  false: the 256-slot storage overflowed.
 template <int STAGE>
-__device__ __forceinline__ bool fs_run_ops_mix(FsMix& t, int16_t* tmp, int16_t* ltk, const uint64_t* htab,
-                                               const int32_t (&cells)[5], uint64_t real) {
+__device__ __forceinline__ bool fs_run_ops_mix(FsMix& t, int16_t* ltk, const uint64_t* htab,
+                                               const int32_t (&cells)[5], uint64_t real, const uint4* lmp) {
     constexpr uint64_t KD = (21ull << 0) | (0ull << 6) | (2ull << 12) | (40ull << 18) | (42ull << 24) |
                             (1ull << 30) | (41ull << 36) | (20ull << 42) | (22ull << 48);  // fs_run_ops
     const uint64_t real0 = real;
@@ -2154,15 +2204,23 @@ __device__ __forceinline__ bool fs_run_ops_mix(FsMix& t, int16_t* tmp, int16_t* 
             need = fs_op_mix(t, (int16_t)key, (unsigned)(op - 1) < 4u, htab[key]);
         }
         if (need) {  // the resizes of a round run together (fs_run_ops), each lane with its own scratch
-            FsetRef r{t.glob ? t.gk : t.lk, t.glob ? 2 : 2 * WAVE, &t.m, &t.f, &t.u,
-                      t.glob ? (uint32_t)BK_FSET_SLOTS : (uint32_t)STAGE, htab, 1, &t.dirty};
-            if (!fs_resize_any(r, tmp, lds_tmp(t.glob ? t.lk : ltk, t.glob ? (uint32_t)STAGE : STAGE / 4))) {
+#ifdef BK_SECTION_PROF
+            const uint64_t rt0 = clock64();  // (section slot 15, as fs_resize_any)
+            const bool rok = fs_resize_mix<STAGE>(t, ltk, htab);
+            const uint64_t rex = __builtin_amdgcn_read_exec();
+            if ((uint32_t)__lane_id() == (uint32_t)__builtin_ctzll(rex)) atomicAdd(&g_sections[15], clock64() - rt0);
+#else
+            const bool rok = fs_resize_mix<STAGE>(t, ltk, htab);
+#endif
+            if (!rok) {
                 if (t.glob) {
                     ok = false;
                     real = 0;
                 } else {
                     t.glob = true;
                     t.m = m0; t.f = f0; t.u = u0;
+                    const uint4 lm = *lmp;  // (the stored mask: nothing was written back yet)
+                    t.set_live_mask(lm.x, lm.y, lm.z, lm.w);
                     real = real0;
                 }
             }
@@ -2173,11 +2231,12 @@ __device__ __forceinline__ bool fs_run_ops_mix(FsMix& t, int16_t* tmp, int16_t* 
 }
 
 // place_frontier<STAGE> for k_rollout_fr (hdr and ltk set, no RECOPY): stage, one op loop
-// for every lane, write-back of the staged lanes' dirty chunks
+// for every lane, write-back of the staged lanes' dirty chunks.  *lmp (live_masks) is
+// the table's live-slot mask, kept up to date by the ops and the resizes and written back
 template <int STAGE, typename Mark>
 __device__ __forceinline__ bool place_frontier_onepass(FsLane* fl, int p, int16_t* lk, const uint64_t* htab,
                                                        const int32_t (&cells)[5], uint64_t real, Mark mark,
-                                                       uint16_t* hdr, int16_t* ltk) {
+                                                       uint16_t* hdr, int16_t* ltk, uint4* lmp) {
     static_assert(STAGE > 0 && STAGE <= STAGE_EAGER_MAX && STAGE <= 256, "an eager stage; dirty holds 32 chunks");
     bk_fset* gfs = &fl->s;
     const bk_u4_alias* src4 = reinterpret_cast<const bk_u4_alias*>(gfs->key[p]);
@@ -2186,7 +2245,13 @@ __device__ __forceinline__ bool place_frontier_onepass(FsLane* fl, int p, int16_
     for (int i = 0; i < STAGE / 8; ++i) pre[i] = src4[i];
     const uint16_t m0 = hdr[0], f0 = hdr[1], u0 = hdr[2];
     bk_u32_alias* lw = reinterpret_cast<bk_u32_alias*>(lk);
-    FsMix t{lk, gfs->key[p], m0 >= (uint16_t)STAGE, m0, f0, u0, 0u};
+    FsMix t{lk, gfs->key[p], m0 >= (uint16_t)STAGE, m0, f0, u0, 0u, lw + (STAGE / 2) * WAVE};
+    {
+        // (locate loaded the same 16 bytes earlier in the ply: loaded again, from a line in
+        // the L1 / L2, rather than held in four registers across the apply and the ops windows)
+        const uint4 lm = *lmp;
+        t.set_live_mask(lm.x, lm.y, lm.z, lm.w);
+    }
     if (!t.glob) {
 #pragma unroll
         for (int i = 0; i < STAGE / 8; ++i) {
@@ -2199,7 +2264,7 @@ __device__ __forceinline__ bool place_frontier_onepass(FsLane* fl, int p, int16_
         }
     }
     mark(8);
-    const bool ok = fs_run_ops_mix<STAGE>(t, fl->tmp, ltk, htab, cells, real);
+    const bool ok = fs_run_ops_mix<STAGE>(t, ltk, htab, cells, real, lmp);
     mark(9);
     if (!t.glob) {
         bk_u4_alias* dst4 = reinterpret_cast<bk_u4_alias*>(gfs->key[p]);
@@ -2213,6 +2278,10 @@ __device__ __forceinline__ bool place_frontier_onepass(FsLane* fl, int p, int16_
     if (t.m != m0) hdr[0] = t.m;
     if (t.f != f0) hdr[1] = t.f;
     if (t.u != u0) hdr[2] = t.u;
+    // (nearly every move changes the mask: stored without a compare, which would need the
+    // loaded mask kept in four registers across the op loop; the store goes into the line
+    // the header's stores go to)
+    *lmp = t.live_mask();
     return ok;
 }
 
@@ -2688,6 +2757,51 @@ __device__ __forceinline__ uint16_t* slab_hdr(const Slab& slab, int p) {
     return reinterpret_cast<uint16_t*>(&slab.word(SLAB_HDR_BASE)) + 3 * p;
 }
 
+// k_rollout_fr keeps, per player, 128 bits next to the game: bit s is set iff key[s] >= 0,
+// for a table of <= 128 slots (a 256-slot table has no mask: its words are undefined).
+// Established by init_live_masks when a game starts, kept by FsMix::put and fs_resize_mix,
+// read by locate_move_frontier<2, true>.  Their home (in_slab, uniform over the launch):
+// with Philox draws and no carried RNG state the slab's compat-RNG words, which lie in the
+// line of the table headers that every ply reads anyway; else (the words hold the seats'
+// MT cursors) the record's padding, one more line per ply.  One code path serves both: a
+// second path that rebuilt the masks per ply for the compat mode cost the Philox mode
+// 1.3 - 1.8 % through register allocation alone (profiles/r09/sweeps/r09a).
+__device__ __forceinline__ uint4* live_masks(const Slab& slab, FsLane* fl, bool in_slab) {
+    static_assert(sizeof(fl->pad) >= 4 * sizeof(uint4) && offsetof(FsLane, pad) % 16 == 0,
+                  "four masks fit the padding");
+    return in_slab ? reinterpret_cast<uint4*>(&slab.word(SLAB_RNG_BASE)) : reinterpret_cast<uint4*>(fl->pad);
+}
+
+// slots 8 i .. 8 i + 7 of a table (one uint4) into its live-slot mask l (chunks i >= 16, of
+// a 256-slot table, leave it alone)
+__device__ __forceinline__ void live_chunk(const uint4& v, uint32_t i, uint4& l) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t dead = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dead |= (((w[j] >> 15) & 1u) | ((w[j] >> 30) & 2u)) << (2 * j);
+    const uint32_t b = (~dead & 0xFFu) << ((i & 3u) * 8u), wd = i >> 2;
+    l.x |= wd == 0u ? b : 0u;
+    l.y |= wd == 1u ? b : 0u;
+    l.z |= wd == 2u ? b : 0u;
+    l.w |= wd == 3u ? b : 0u;
+}
+
+// the live-slot masks lm[0..3] of a game's four tables as start_game left them in record
+// fs (the headers in the slab): one pass over each table of <= 128 slots, 8 slots per load
+// (BK_SEM_ROLLOUT, whose tables fs_copy_dev lays out anew)
+__device__ __forceinline__ void init_live_masks(const bk_fset* fs, const Slab& slab, uint4* lm) {
+#pragma unroll 1
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t mask = *slab_hdr(slab, q);
+        const bk_u4_alias* k4 = reinterpret_cast<const bk_u4_alias*>(fs->key[q]);
+        uint4 l = make_uint4(0u, 0u, 0u, 0u);
+        const uint32_t nv = mask < 128u ? (mask + 1u) / 8u : 0u;
+#pragma unroll 2
+        for (uint32_t i = 0; i < nv; ++i) live_chunk(k4[i], i, l);
+        lm[q] = l;
+    }
+}
+
 // a plain copy of the four tables: slots 0..mask of each (the rest is never read) and
 // the counters, as uint4
 __device__ __forceinline__ void copy_fset(bk_fset* dst, const bk_fset* src) {
@@ -2730,6 +2844,37 @@ __device__ __forceinline__ void copy_fset_in(bk_fset* dst, const Slab& slab, con
         const int nv = (int)(masks[q] + 1u) / 8;  // 8 slots per uint4
 #pragma unroll 2
         for (int i = 0; i < nv; ++i) d4[i] = s4[i];
+    }
+}
+
+// copy_fset_in that also builds the tables' live-slot masks lm[0..3] (live_masks) from the
+// words it copies: a pass of its own over the copied tables waited for 64 more loads at the
+// start of every game (-1 % of k_rollout_fr's launch, profiles/r09/sweeps/r09a)
+__device__ __forceinline__ void copy_fset_in_live(bk_fset* dst, const Slab& slab, const bk_fset* src, uint4* lm) {
+    const bk_u4_alias* tail_s = reinterpret_cast<const bk_u4_alias*>(&src->mask[0]);
+    const uint4 t0 = tail_s[0], t1 = tail_s[1];  // mask[4] fill[4] used[4] reserved[4]
+    const uint32_t masks[4] = {t0.x & 0xFFFFu, t0.x >> 16, t0.y & 0xFFFFu, t0.y >> 16};
+    const uint32_t fills[4] = {t0.z & 0xFFFFu, t0.z >> 16, t0.w & 0xFFFFu, t0.w >> 16};
+    const uint32_t useds[4] = {t1.x & 0xFFFFu, t1.x >> 16, t1.y & 0xFFFFu, t1.y >> 16};
+    slab.word(SLAB_HDR_BASE + 0) = masks[0] | (fills[0] << 16);
+    slab.word(SLAB_HDR_BASE + 1) = useds[0] | (masks[1] << 16);
+    slab.word(SLAB_HDR_BASE + 2) = fills[1] | (useds[1] << 16);
+    slab.word(SLAB_HDR_BASE + 3) = masks[2] | (fills[2] << 16);
+    slab.word(SLAB_HDR_BASE + 4) = useds[2] | (masks[3] << 16);
+    slab.word(SLAB_HDR_BASE + 5) = fills[3] | (useds[3] << 16);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const bk_u4_alias* s4 = reinterpret_cast<const bk_u4_alias*>(src->key[q]);
+        bk_u4_alias* d4 = reinterpret_cast<bk_u4_alias*>(dst->key[q]);
+        const uint32_t nv = (masks[q] + 1u) / 8u;  // 8 slots per uint4
+        uint4 l = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll 2
+        for (uint32_t i = 0; i < nv; ++i) {
+            const uint4 v = s4[i];
+            d4[i] = v;
+            live_chunk(v, i, l);
+        }
+        lm[q] = l;
     }
 }
 
@@ -2867,9 +3012,10 @@ __device__ __forceinline__ void finish_game(const RolloutArgs& a, Game& g, const
     g.pid = -1;
 }
 
-template <bool FR>
+// LIVE (k_rollout_fr): the tables' live-slot masks are set up in lm[0..3] (live_masks)
+template <bool FR, bool LIVE = false>
 __device__ __forceinline__ void start_game(const RolloutArgs& a, Game& g, const Slab& slab, uint32_t slot, int32_t pid,
-                                           const uint64_t* htab) {
+                                           const uint64_t* htab, uint4* lm = nullptr) {
     int32_t ri = a.root_index ? a.root_index[pid] : (pid % a.n_roots);
     bool bad_root = false;
     if (ri < 0 || ri >= a.n_roots) {  // device-path input error: flagged, never read out of bounds
@@ -2925,8 +3071,12 @@ __device__ __forceinline__ void start_game(const RolloutArgs& a, Game& g, const 
                 hq[1] = d->fill[q];
                 hq[2] = d->used[q];
             }
+            if constexpr (LIVE) init_live_masks(d, slab, lm);
         } else {
-            copy_fset_in(&a.fslab[slot].s, slab, a.root_sets + ri);
+            if constexpr (LIVE)
+                copy_fset_in_live(&a.fslab[slot].s, slab, a.root_sets + ri, lm);
+            else
+                copy_fset_in(&a.fslab[slot].s, slab, a.root_sets + ri);
         }
     }
     g.hmask = a.seat_masks ? (a.seat_masks[pid] & 0xFu) : (uint32_t)a.cfg.heuristic_seats;
@@ -3096,6 +3246,9 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a) {
     uint32_t* const my = lds + wv * AREA;
     const bool arena = a.cfg.semantics != BK_SEM_ROLLOUT;  // passes allowed
     const bool advance = a.cfg.semantics == BK_SEM_ADVANCE;
+    // k_rollout_fr carries each table's live-slot mask from ply to ply (live_masks): in the
+    // slab words of the compat RNG when no RNG state lives there
+    const bool lm_in_slab = FR && !HEUR && a.cfg.rng == BK_RNG_PHILOX && a.rng_io == nullptr;
 
     Game g;
     g.pid = -1;
@@ -3127,7 +3280,10 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a) {
                 if (next >= a.n_playouts) { done = true; break; }
                 // bk_arena_step: a game whose search is still running is left untouched
                 if (HEUR && a.forced && a.forced[next] == BK_FORCE_SKIP) continue;
-                start_game<FR>(a, g, slab, slot, next, htab);
+                if constexpr (FR && !HEUR)
+                    start_game<true, true>(a, g, slab, slot, next, htab, live_masks(slab, &a.fslab[slot], lm_in_slab));
+                else
+                    start_game<FR>(a, g, slab, slot, next, htab);
             }
             if (arena) {
                 // (ADVANCE: once the placement budget is used nobody passes any more -- the
@@ -3286,7 +3442,12 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a) {
                                    ar, ac, h_unc);
                 if (h_unc) g.status |= BK_STATUS_UNCERT;
             } else {
-                locate_move_frontier(orow, kk, rows_lds, fs->key[p], fmask, ar, ac);
+                if constexpr (HEUR) {
+                    locate_move_frontier(orow, kk, rows_lds, fs->key[p], fmask, ar, ac);
+                } else {
+                    const uint4 lmv = live_masks(slab, &a.fslab[slot], lm_in_slab)[p];
+                    locate_move_frontier<2, true>(orow, kk, rows_lds, fs->key[p], fmask, ar, ac, lmv);
+                }
             }
         } else {
             locate_move_lds(orow, kk, rows_lds, ar, ac);
@@ -3355,7 +3516,8 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a) {
                                              lk + 2 * WAVE * (STG / 2));
             else  // k_rollout_fr: one op loop for the staged and the in-place tables of the wave
                 placed = place_frontier_onepass<STG>(&a.fslab[slot], p, lk, htab, cells, real, mark,
-                                                     slab_hdr(slab, p), lk + 2 * WAVE * (STG / 2));
+                                                     slab_hdr(slab, p), lk + 2 * WAVE * (STG / 2),
+                                                     live_masks(slab, &a.fslab[slot], lm_in_slab) + p);
             if (!placed) g.status |= 2u;
         }
         SECT(6);

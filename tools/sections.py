@@ -82,6 +82,34 @@ def run():
         read("k_mcts", {"games": games, "iterations": 16, "kernel_ms": gpu.last_kernel_ms()})
 
 
+def run_fr():
+    """k_rollout_fr alone (run()'s frontier-order launch): what an A/B of that kernel needs."""
+    os.environ["BK_LIB_PATH"] = LIB
+    sys.path.insert(0, ROOT)
+    import ctypes as C
+
+    import numpy as np
+    from reinforcementlearning_blokus_amd import _native as N
+    from reinforcementlearning_blokus_amd.gpu import BlokusGPU, empty_state
+    gpu = BlokusGPU(0)
+    L = N.load()
+    buf = (C.c_uint64 * 16)()
+    G, R = 256, 1024
+    froots, fsets = gpu.rollout_frontier(empty_state(), N.fset_new(1), G, semantics=N.SEM_ADVANCE,
+                                         rng=N.RNG_PHILOX, seed=5, max_plies=20,
+                                         root_index=np.zeros(G, dtype=np.int32))
+    idx = np.repeat(np.arange(G, dtype=np.int32), R)
+    L.bk_debug_sections(gpu.handle._h, buf, 16, 1)
+    gpu.rollout_frontier(froots, fsets, G * R, semantics=N.SEM_ARENA, rng=N.RNG_PHILOX, seed=1, root_index=idx)
+    rc = L.bk_debug_sections(gpu.handle._h, buf, 16, 1)
+    assert rc == 0, rc
+    tot = sum(buf)
+    nm = {**NAMES, **FR_NAMES}
+    rows = {nm.get(i, str(i)): round(buf[i] / tot, 4) for i in range(16) if buf[i]}
+    print(json.dumps({"run": "k_rollout_fr", "kernel_ms": gpu.last_kernel_ms(), "cycles": tot, "share": rows,
+                      "raw": list(buf)}), flush=True)
+
+
 def run_mcts():
     """k_mcts sections in the config-5 regime (65,536 searches, deep trees: a warm-up of
     `iterations` then a measured chunk of 64 more) and k_mcts_h (heuristic rollouts)."""
@@ -162,6 +190,8 @@ def run_coop():
 if __name__ == "__main__":
     if "--build" in sys.argv:
         build()
+    elif "--fr" in sys.argv:
+        run_fr()
     elif "--coop" in sys.argv:
         run_coop()
     elif "--mcts" in sys.argv:
