@@ -602,37 +602,64 @@ __device__ __forceinline__ void locate_move(int gs, uint32_t kk, const uint32_t 
     out_c = found_c;
 }
 
-// locate_move with the mover's B/C rows in LDS (rows[R * WAVE] = {B[R], C[R]}, R < 20):
-// the per-lane cell rows become per-lane LDS addresses instead of 5-way register
-// selects.  Cells beyond the orientation's count repeat cell 0 (ORing a term twice is
-// harmless).  Anchor rows past 20 - height cannot hold the piece: they are evaluated
-// at the last valid row (so every read stays in rows 0..19) and then dropped.
-__device__ __forceinline__ void locate_move_lds(const OrientRow& orow, uint32_t kk, const uint2* rows, int& out_r,
-                                                int& out_c) {
-    const uint32_t info = orow.info;
-    const int n = (int)((info >> 8) & 0xFFu);
-    const int rlim = 20 - (int)((info >> 16) & 0xFFu);
+// An orientation's cells against the mover's B/C rows in LDS (rows[R * WAVE] = {B[R],
+// C[R]}, R < 20): the per-lane cell rows become per-lane LDS addresses instead of 5-way
+// register selects.  Cell k = (cd[k], sh[k]) reads row r + cd[k] at base[k][r * WAVE] and
+// shifts it by its column sh[k].  Cells beyond the orientation's count n repeat cell 0
+// (ORing a term twice is harmless).  cell_of(k, n): the packed cell (row << 8 | column)
+// that cell k of n stands for
+struct LocCells {
+    int n, rlim;  // cells; last anchor row that can hold the piece (20 - height)
     const uint2* base[5];
     uint32_t sh[5];
+    int cd[5];
+};
+template <typename CellOf>
+__device__ __forceinline__ LocCells locate_cells_of(uint32_t info, const uint2* rows, CellOf cell_of) {
+    LocCells lc;
+    lc.n = (int)((info >> 8) & 0xFFu);
+    lc.rlim = 20 - (int)((info >> 16) & 0xFFu);
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        const uint32_t cell = k < n ? orow.cell[k] : orow.cell[0];
-        base[k] = rows + (cell >> 8) * WAVE;
-        sh[k] = cell & 0xFFu;
+        const uint32_t cell = cell_of(k, lc.n);
+        lc.base[k] = rows + (cell >> 8) * WAVE;
+        lc.sh[k] = cell & 0xFFu;
+        lc.cd[k] = (int)(cell >> 8);
     }
+    return lc;
+}
+__device__ __forceinline__ LocCells locate_cells(const OrientRow& orow, const uint2* rows) {
+    return locate_cells_of(orow.info, rows, [&](int k, int n) { return k < n ? orow.cell[k] : orow.cell[0]; });
+}
+__device__ __forceinline__ LocCells locate_cells(int gs, const uint2* rows) {
+    return locate_cells_of(kInfo[gs], rows, [&](int k, int n) { return kCells[gs][k < n ? k : 0]; });
+}
+
+// The legal anchors of anchor row r (bit c: the piece fits with its box corner at (r, c)):
+// every cell on a C bit (ac) and none on a B bit (ab), five LDS reads.  Anchor rows past
+// rlim cannot hold the piece: they are evaluated at the last valid row (so every read
+// stays in rows 0..19) and then dropped.
+__device__ __forceinline__ uint32_t anchor_row(const LocCells& lc, int r) {
+    const int rr = r < lc.rlim ? r : lc.rlim;
+    uint2 v[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) v[k] = lc.base[k][rr * WAVE];
+    uint32_t ab = BITOP3(v[0].x >> lc.sh[0], v[1].x >> lc.sh[1], v[2].x >> lc.sh[2], LUT_OR3);
+    uint32_t ac = BITOP3(v[0].y >> lc.sh[0], v[1].y >> lc.sh[1], v[2].y >> lc.sh[2], LUT_OR3);
+    ab = BITOP3(ab, v[3].x >> lc.sh[3], v[4].x >> lc.sh[4], LUT_OR3);
+    ac = BITOP3(ac, v[3].y >> lc.sh[3], v[4].y >> lc.sh[4], LUT_OR3);
+    return r <= lc.rlim ? (ac & ~ab) : 0u;
+}
+
+// locate_move with the mover's B/C rows in LDS (locate_cells, anchor_row)
+__device__ __forceinline__ void locate_move_lds(const OrientRow& orow, uint32_t kk, const uint2* rows, int& out_r,
+                                                int& out_c) {
+    const LocCells lc = locate_cells(orow, rows);
     int found_r = -1, found_c = 0;
     uint32_t rem = kk;
 #pragma unroll
     for (int r = 0; r < 20; ++r) {
-        const int rr = r < rlim ? r : rlim;
-        uint2 v[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) v[k] = base[k][rr * WAVE];
-        uint32_t ab = BITOP3(v[0].x >> sh[0], v[1].x >> sh[1], v[2].x >> sh[2], LUT_OR3);
-        uint32_t ac = BITOP3(v[0].y >> sh[0], v[1].y >> sh[1], v[2].y >> sh[2], LUT_OR3);
-        ab = BITOP3(ab, v[3].x >> sh[3], v[4].x >> sh[4], LUT_OR3);
-        ac = BITOP3(ac, v[3].y >> sh[3], v[4].y >> sh[4], LUT_OR3);
-        const uint32_t ok = r <= rlim ? (ac & ~ab) : 0u;
+        const uint32_t ok = anchor_row(lc, r);
         const uint32_t pc = __builtin_popcount(ok);
         if (found_r < 0) {
             if (rem < pc) {
@@ -652,6 +679,16 @@ __device__ __forceinline__ void locate_move_lds(int gs, uint32_t kk, const uint2
     locate_move_lds(orient_row(gs), kk, rows, out_r, out_c);
 }
 
+// Frontier tables hold int16 slots, read two per dword: the low (hi = 0) or high slot of
+// dword w, and slot j of the slots packed in w[] (the key, or a negative FS_UNUSED /
+// FS_DUMMY)
+__host__ __device__ __forceinline__ int fs_key16(uint32_t w, int hi) {
+    return (int)(int16_t)(hi ? (w >> 16) : (w & 0xFFFFu));
+}
+__host__ __device__ __forceinline__ int fs_key16(const uint32_t* w, int j) { return fs_key16(w[j >> 1], j & 1); }
+// bits 0 and 1: the low and the high slot of dword w hold no key (their sign bits)
+__device__ __forceinline__ uint32_t fs_dead2(uint32_t w) { return ((w >> 15) & 1u) | ((w >> 30) & 2u); }
+
 // Frontier-order variant (BK_ORDER_FRONTIER): the kk-th anchor of orientation gs in the
 // reference's list order (engine/move_generator.py:261-559).  Pass 1 writes the legal
 // anchors of gs over the B half of each LDS row.  Pass 2 walks the mover's frontier set
@@ -660,29 +697,44 @@ __device__ __forceinline__ void locate_move_lds(int gs, uint32_t kk, const uint2
 // Pass 1 of locate_move_frontier alone: the legal anchors of gs over the C half of each
 // LDS row (rows[r].y; the B half stays)
 __device__ __forceinline__ void locate_pass1(int gs, uint2* rows) {
-    const uint32_t info = kInfo[gs];
-    const int n = (int)((info >> 8) & 0xFFu);
-    const int rlim = 20 - (int)((info >> 16) & 0xFFu);
-    const uint2* base[5];
-    uint32_t sh[5];
+    const LocCells lc = locate_cells(gs, rows);
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const uint32_t cell = kCells[gs][k < n ? k : 0];
-        base[k] = rows + (cell >> 8) * WAVE;
-        sh[k] = cell & 0xFFu;
+    for (int r = 0; r < 20; ++r) rows[r * WAVE].y = anchor_row(lc, r);
+}
+
+// Pass 2's scan of a 16-slot batch w (slots b0 .. b0 + 15 of a table of mask + 1 slots):
+// bit j marks a slot that can add an anchor, i.e. holds a frontier cell f whose anchor rows
+// fr - H + 1 .. fr (piece height H, hmask = 2^H - 1) have a legal anchor left (arows)
+__device__ __forceinline__ uint32_t locate_batch_rel(const uint32_t (&w)[8], int b0, int mask, uint32_t arows, int H,
+                                                     uint32_t hmask) {
+    uint32_t rel = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int f = fs_key16(w, j);
+        const int fr = f >= 0 ? f / 20 : 0;
+        rel |= (f >= 0 && b0 + j <= mask && ((arows >> (fr + 5 - H)) & hmask)) ? (1u << j) : 0u;
     }
+    return rel;
+}
+
+// Pass 2's end: the rem-th new anchor of frontier cell hit_f, in cell order (hit_f < 0: no
+// anchor, out_r -1).  rows[.].y holds the anchors not yet counted.
+__device__ __forceinline__ void locate_resolve(const LocCells& lc, const uint2* rows, int hit_f, uint32_t rem,
+                                               int& out_r, int& out_c) {
+    int found_r = -1, found_c = 0;
+    if (hit_f >= 0) {
+        const int fr = hit_f / 20, fc = hit_f - 20 * fr;
 #pragma unroll
-    for (int r = 0; r < 20; ++r) {
-        const int rr = r < rlim ? r : rlim;
-        uint2 v[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) v[k] = base[k][rr * WAVE];
-        uint32_t ab = BITOP3(v[0].x >> sh[0], v[1].x >> sh[1], v[2].x >> sh[2], LUT_OR3);
-        uint32_t ac = BITOP3(v[0].y >> sh[0], v[1].y >> sh[1], v[2].y >> sh[2], LUT_OR3);
-        ab = BITOP3(ab, v[3].x >> sh[3], v[4].x >> sh[4], LUT_OR3);
-        ac = BITOP3(ac, v[3].y >> sh[3], v[4].y >> sh[4], LUT_OR3);
-        rows[r * WAVE].y = r <= rlim ? (ac & ~ab) : 0u;
+        for (int k = 0; k < 5; ++k) {
+            if (k >= lc.n || found_r >= 0) continue;
+            const int ar = fr - lc.cd[k], acl = fc - (int)lc.sh[k];
+            if (ar < 0 || acl < 0) continue;
+            if (!((rows[ar * WAVE].y >> acl) & 1u)) continue;
+            if (rem == 0u) { found_r = ar; found_c = acl; } else { --rem; }
+        }
     }
+    out_r = found_r;
+    out_c = found_c;
 }
 
 // RS: uint4 distance between 16-slot runs of the table (2: a plain array; 64: the lane
@@ -694,32 +746,16 @@ __device__ __forceinline__ void locate_move_frontier(const OrientRow& orow, uint
                                                      const int16_t* key, int mask, int& out_r, int& out_c,
                                                      uint4 lmv = uint4{}) {
     const uint32_t info = orow.info;
-    const int n = (int)((info >> 8) & 0xFFu);
-    const int rlim = 20 - (int)((info >> 16) & 0xFFu);
-    const uint2* base[5];
-    uint32_t sh[5];
-    int cd[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const uint32_t cell = k < n ? orow.cell[k] : orow.cell[0];
-        base[k] = rows + (cell >> 8) * WAVE;
-        sh[k] = cell & 0xFFu;
-        cd[k] = (int)(cell >> 8);
-    }
+    const LocCells lc = locate_cells(orow, rows);
+    const int n = lc.n;
+    const int (&cd)[5] = lc.cd;
+    const uint32_t (&sh)[5] = lc.sh;
     uint32_t arows = 0;  // bit r + 4: anchor row r holds a legal anchor (a superset later)
 #pragma unroll
     for (int r = 0; r < 20; ++r) {
-        const int rr = r < rlim ? r : rlim;
-        uint2 v[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) v[k] = base[k][rr * WAVE];
-        uint32_t ab = BITOP3(v[0].x >> sh[0], v[1].x >> sh[1], v[2].x >> sh[2], LUT_OR3);
-        uint32_t ac = BITOP3(v[0].y >> sh[0], v[1].y >> sh[1], v[2].y >> sh[2], LUT_OR3);
-        ab = BITOP3(ab, v[3].x >> sh[3], v[4].x >> sh[4], LUT_OR3);
-        ac = BITOP3(ac, v[3].y >> sh[3], v[4].y >> sh[4], LUT_OR3);
         // the anchors go to the C half: row r's C word is not read again (later rows
         // read rows >= r + 1), and the B half stays intact for frontier_ops
-        const uint32_t okr = r <= rlim ? (ac & ~ab) : 0u;
+        const uint32_t okr = anchor_row(lc, r);
         rows[r * WAVE].y = okr;
         arows |= okr ? (1u << (r + 4)) : 0u;
     }
@@ -771,13 +807,7 @@ __device__ __forceinline__ void locate_move_frontier(const OrientRow& orow, uint
             const uint32_t w[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
             // the batch's slots that can add an anchor, then one divergent pass over just
             // those: the wave runs the row reads max-over-lanes-of-relevant-slots times
-            uint32_t rel = 0;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int f = (int)(int16_t)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu));
-                const int fr = f >= 0 ? f / 20 : 0;
-                rel |= (f >= 0 && b0 + j <= mask && ((arows >> (fr + 5 - H)) & hmask)) ? (1u << j) : 0u;
-            }
+            uint32_t rel = locate_batch_rel(w, b0, mask, arows, H, hmask);
 #pragma unroll 1
             while (rel && hit_f < 0) {
                 const int j = __builtin_ctz(rel);
@@ -785,7 +815,7 @@ __device__ __forceinline__ void locate_move_frontier(const OrientRow& orow, uint
                 uint32_t wj = w[0];
 #pragma unroll
                 for (int q = 1; q < 8; ++q) wj = (j >> 1) == q ? w[q] : wj;
-                count_key((int)(int16_t)((j & 1) ? (wj >> 16) : (wj & 0xFFFFu)));
+                count_key(fs_key16(wj, j & 1));
             }
             qa = na; qb = nb;
         }
@@ -813,7 +843,7 @@ __device__ __forceinline__ void locate_move_frontier(const OrientRow& orow, uint
                     const uint32_t w[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
                     uint32_t dead = 0;
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) dead |= (((w[i] >> 15) & 1u) | ((w[i] >> 30) & 2u)) << (2 * i);
+                    for (int i = 0; i < 8; ++i) dead |= fs_dead2(w[i]) << (2 * i);
                     const uint32_t valid = (b == 0 && mask < 15) ? 0xFFu : 0xFFFFu;
                     lm[b >> 1] |= (~dead & valid) << ((b & 1) * 16);
                     qa = na; qb = nb;
@@ -848,21 +878,7 @@ __device__ __forceinline__ void locate_move_frontier(const OrientRow& orow, uint
             if (hit_f >= 0 || (nxt < 0 && !(lm[0] | lm[1] | lm[2] | lm[3]))) break;
         }
     }
-    int found_r = -1, found_c = 0;
-    if (hit_f >= 0) {  // the (kk - cnt)-th new anchor of frontier cell hit_f, in cell order
-        const int fr = hit_f / 20, fc = hit_f - 20 * fr;
-        uint32_t rem = kk - cnt;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            if (k >= n || found_r >= 0) continue;
-            const int ar = fr - cd[k], acl = fc - (int)sh[k];
-            if (ar < 0 || acl < 0) continue;
-            if (!((rows[ar * WAVE].y >> acl) & 1u)) continue;
-            if (rem == 0u) { found_r = ar; found_c = acl; } else { --rem; }
-        }
-    }
-    out_r = found_r;
-    out_c = found_c;
+    locate_resolve(lc, rows, hit_f, kk - cnt, out_r, out_c);
 }
 template <int RS = 2>
 __device__ __forceinline__ void locate_move_frontier(int gs, uint32_t kk, uint2* rows, const int16_t* key, int mask,
@@ -883,33 +899,14 @@ template <int RS = 2>
 __device__ __forceinline__ void locate_frontier_pair(int gs, uint32_t kk, uint2* rows, const int16_t* key, int mask,
                                                      bool odd, int& out_r, int& out_c) {
     const uint32_t info = kInfo[gs];
-    const int n = (int)((info >> 8) & 0xFFu);
-    const int rlim = 20 - (int)((info >> 16) & 0xFFu);
-    const uint2* base[5];
-    uint32_t sh[5];
-    int cd[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const uint32_t cell = kCells[gs][k < n ? k : 0];
-        base[k] = rows + (cell >> 8) * WAVE;
-        sh[k] = cell & 0xFFu;
-        cd[k] = (int)(cell >> 8);
-    }
+    const LocCells lc = locate_cells(gs, rows);
+    const int n = lc.n;
+    const int (&cd)[5] = lc.cd;
+    const uint32_t (&sh)[5] = lc.sh;
     const int r0 = odd ? 10 : 0;
     uint32_t okv[10];
 #pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const int r = r0 + i;
-        const int rr = r < rlim ? r : rlim;
-        uint2 v[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) v[k] = base[k][rr * WAVE];
-        uint32_t ab = BITOP3(v[0].x >> sh[0], v[1].x >> sh[1], v[2].x >> sh[2], LUT_OR3);
-        uint32_t ac = BITOP3(v[0].y >> sh[0], v[1].y >> sh[1], v[2].y >> sh[2], LUT_OR3);
-        ab = BITOP3(ab, v[3].x >> sh[3], v[4].x >> sh[4], LUT_OR3);
-        ac = BITOP3(ac, v[3].y >> sh[3], v[4].y >> sh[4], LUT_OR3);
-        okv[i] = r <= rlim ? (ac & ~ab) : 0u;
-    }
+    for (int i = 0; i < 10; ++i) okv[i] = anchor_row(lc, r0 + i);
     uint32_t arows = 0;  // bit r + 4: anchor row r holds a legal anchor (a superset later)
 #pragma unroll
     for (int i = 0; i < 10; ++i) {
@@ -939,13 +936,7 @@ __device__ __forceinline__ void locate_frontier_pair(int gs, uint32_t kk, uint2*
         const int nb0 = b0 + 16 <= mask ? b0 + 16 : b0;
         const uint4 na = k4[(nb0 >> 4) * RS], nb = k4[(nb0 >> 4) * RS + 1];
         const uint32_t w[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-        uint32_t rel = 0;  // as locate_move_frontier (the pair's lanes hold the same mask)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int f = (int)(int16_t)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu));
-            const int fr = f >= 0 ? f / 20 : 0;
-            rel |= (f >= 0 && b0 + j <= mask && ((arows >> (fr + 5 - H)) & hmask)) ? (1u << j) : 0u;
-        }
+        uint32_t rel = locate_batch_rel(w, b0, mask, arows, H, hmask);  // (the pair's lanes hold the same mask)
 #pragma unroll 1
         while (rel && hit_f < 0) {
             const int j = __builtin_ctz(rel);
@@ -953,7 +944,7 @@ __device__ __forceinline__ void locate_frontier_pair(int gs, uint32_t kk, uint2*
             uint32_t wj = w[0];
 #pragma unroll
             for (int q = 1; q < 8; ++q) wj = (j >> 1) == q ? w[q] : wj;
-            const int f = (int)(int16_t)((j & 1) ? (wj >> 16) : (wj & 0xFFFFu));
+            const int f = fs_key16(wj, j & 1);
             const int fr = f / 20, fc = f - 20 * fr;
             uint32_t hm[3], tot = 0;
 #pragma unroll
@@ -972,21 +963,7 @@ __device__ __forceinline__ void locate_frontier_pair(int gs, uint32_t kk, uint2*
         }
         qa = na; qb = nb;
     }
-    int found_r = -1, found_c = 0;
-    if (hit_f >= 0) {  // the (kk - cnt)-th new anchor of frontier cell hit_f, in cell order
-        const int fr = hit_f / 20, fc = hit_f - 20 * fr;
-        uint32_t rem = kk - cnt;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            if (k >= n || found_r >= 0) continue;
-            const int ar = fr - cd[k], acl = fc - (int)sh[k];
-            if (ar < 0 || acl < 0) continue;
-            if (!((rows[ar * WAVE].y >> acl) & 1u)) continue;
-            if (rem == 0u) { found_r = ar; found_c = acl; } else { --rem; }
-        }
-    }
-    out_r = found_r;
-    out_c = found_c;
+    locate_resolve(lc, rows, hit_f, kk - cnt, out_r, out_c);
 }
 
 // The set operations of update_frontier_after_move that CHANGE the mover's set.  The
@@ -1500,16 +1477,20 @@ __host__ __device__ __forceinline__ FsetRef fs_ref(bk_fset* s, int p, const uint
     return FsetRef{s->key[p], 2, &s->mask[p], &s->fill[p], &s->used[p], BK_FSET_SLOTS, htab};
 }
 
-// set_insert_clean: first unused slot of the probe sequence.  The linear probes walk
-// the slots after i, but the next perturbation step starts from i itself, not from the
-// last slot probed (CPython advances `entry`, not `i`; checked against CPython 3.10's
-// set.copy() in tests/test_fset_copy.py)
-__host__ __device__ inline void fs_insert_clean(FsetRef t, uint32_t mask, int16_t k) {
-    const uint64_t h = t.hash[k];
-    uint64_t perturb = h;
-    uint32_t i = (uint32_t)h & mask, e = i;
-    uint32_t left = i + FS_PROBES <= mask ? FS_PROBES : 0u;
-    while (t.at(e) != FS_UNUSED) {
+// The probe sequence of hash h in a table of mask + 1 slots (set_lookkey / set_add_entry /
+// set_insert_clean, Objects/setobject.c): e is the slot to probe.  From i = hash & mask the
+// 10 slots i .. i + 9 when they fit below mask (LINEAR_PROBES 9), else slot i alone, then
+// i = (5 i + 1 + perturb) & mask with perturb >>= 5.  The linear probes walk the slots
+// after i, but the next perturbation step starts from i itself, not from the last slot
+// probed (CPython advances `entry`, not `i`; checked against CPython 3.10's set.copy() in
+// tests/test_fset_copy.py).  Slot indices stay 32-bit: only the low bits of
+// 5 i + 1 + perturb survive the mask.
+struct FsProbeSeq {
+    uint32_t i, e, left;
+    uint64_t perturb;
+    __host__ __device__ __forceinline__ FsProbeSeq(uint64_t h, uint32_t mask)
+        : i((uint32_t)h & mask), e(i), left(i + FS_PROBES <= mask ? FS_PROBES : 0u), perturb(h) {}
+    __host__ __device__ __forceinline__ void next(uint32_t mask) {
         if (left > 0u) {
             --left;
             ++e;
@@ -1520,7 +1501,13 @@ __host__ __device__ inline void fs_insert_clean(FsetRef t, uint32_t mask, int16_
             left = i + FS_PROBES <= mask ? FS_PROBES : 0u;
         }
     }
-    t.at(e) = k;
+};
+
+// set_insert_clean: first unused slot of the probe sequence
+__host__ __device__ inline void fs_insert_clean(FsetRef t, uint32_t mask, int16_t k) {
+    FsProbeSeq s(t.hash[k], mask);
+    while (t.at(s.e) != FS_UNUSED) s.next(mask);
+    t.at(s.e) = k;
 }
 
 // Occupancy of a table of <= 256 slots in registers: set_insert_clean's probe sequence
@@ -1546,23 +1533,43 @@ struct SlotBits {
 // fs_insert_clean's slot for key hash h in a fresh table of mask + 1 slots whose used
 // slots are `o` (marks the slot used)
 __host__ __device__ __forceinline__ uint32_t fs_clean_slot(uint64_t h, uint32_t mask, SlotBits& o) {
-    uint64_t perturb = h;
-    uint32_t i = (uint32_t)h & mask, e = i;
-    uint32_t left = i + FS_PROBES <= mask ? FS_PROBES : 0u;
+    FsProbeSeq s(h, mask);
 #pragma unroll 1
-    while (o.test(e)) {  // fs_insert_clean's sequence
-        if (left > 0u) {
-            --left;
-            ++e;
-        } else {
-            perturb >>= FS_SHIFT;
-            i = (i * 5u + 1u + (uint32_t)perturb) & mask;
-            e = i;
-            left = i + FS_PROBES <= mask ? FS_PROBES : 0u;
-        }
+    while (o.test(s.e)) s.next(mask);  // fs_insert_clean's sequence
+    o.set(s.e);
+    return s.e;
+}
+
+// The clean re-insert of set.copy() into a fresh table (Board.copy(): fs_recopy_global and
+// the RECOPY tails of place_frontier / place_frontier_dma), from the old table's words in
+// slot order.  The fresh table: k4 (newsize slots, all FS_UNUSED) with the header
+// (newsize - 1, used, used)
+__device__ __forceinline__ void fs_fresh_table(bk_u4_alias* k4, uint32_t newsize, uint32_t used, uint16_t* hm,
+                                               uint16_t* hf, uint16_t* hu) {
+    const uint4 unused = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);  // FS_UNUSED pairs
+#pragma unroll 1
+    for (uint32_t i = 0; i < newsize / 8; ++i) k4[i] = unused;
+    *hm = (uint16_t)(newsize - 1);
+    *hf = (uint16_t)used;
+    *hu = (uint16_t)used;
+}
+// the live keys of one dword w of the old table (a slot pair) go to fresh table dk (nmask + 1
+// slots, used slots o) at fs_clean_slot's slots, never reading dk back
+__device__ __forceinline__ void fs_reinsert_pair(uint32_t w, int16_t* dk, uint32_t nmask, const uint64_t* htab,
+                                                 SlotBits& o) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int16_t k = (int16_t)fs_key16(w, j);
+        if (k >= 0) dk[fs_clean_slot(htab[k], nmask, o)] = k;
     }
-    o.set(e);
-    return e;
+}
+// ... of one 8-slot chunk v
+__device__ __forceinline__ void fs_reinsert_chunk(const uint4& v, int16_t* dk, uint32_t nmask, const uint64_t* htab,
+                                                  SlotBits& o) {
+    fs_reinsert_pair(v.x, dk, nmask, htab, o);
+    fs_reinsert_pair(v.y, dk, nmask, htab, o);
+    fs_reinsert_pair(v.z, dk, nmask, htab, o);
+    fs_reinsert_pair(v.w, dk, nmask, htab, o);
 }
 
 // set_table_resize through a small LDS scratch `tmp` (FsetRef layout; the caller checks
@@ -1640,11 +1647,9 @@ __host__ __device__ inline bool fs_resize(FsetRef t, int16_t* tmp, uint32_t minu
 // resized through the LDS scratch ltmp (fs_resize_lds); else through tmp (fs_resize).
 // The probe sequence of key k (hash h) in table t: the slot e where the search stops (k
 // found, or the first unused slot) with its value kk, and the last dummy seen before it
-// (freeslot, -1 if none).  From i = hash & mask the 10 slots i .. i + 9 when they fit
-// below mask (LINEAR_PROBES 9), else slot i alone, then i = (5 i + 1 + perturb) & mask
-// with perturb >>= 5.  Slot indices stay 32-bit: only the low bits of 5 i + 1 + perturb
-// survive the mask.  One slot per step, as one flat loop (a divergent nested loop costs
-// the wave far more exec-mask bookkeeping than its VALU work).  Reading two or four slots
+// (freeslot, -1 if none), along FsProbeSeq.  One slot per step, as one flat loop (a
+// divergent nested loop costs the wave far more exec-mask bookkeeping than its VALU
+// work).  Reading two or four slots
 // per step from the pair-stored tables measured slower (frontier-order config 3 34.1 ->
 // 33.2 / 33.0 M playouts/s, config 5 17.6 -> 17.1 / 17.0 M; profiles/r05/sweeps/r05f):
 // most chains end at their first or second slot.
@@ -1653,54 +1658,36 @@ __host__ __device__ inline bool fs_resize(FsetRef t, int16_t* tmp, uint32_t minu
 // linear run from registers, loading the next chunk only when the sequence leaves it.
 __host__ __device__ inline void fs_probe(FsetRef t, int16_t k, uint64_t h, uint32_t mask, uint32_t& e_out,
                                          int16_t& kk_out, int32_t& freeslot) {
-    uint64_t perturb = h;
-    uint32_t i = (uint32_t)h & mask, e = i;
-    uint32_t left = i + FS_PROBES <= mask ? FS_PROBES : 0u;
+    FsProbeSeq s(h, mask);
     freeslot = -1;
     int16_t kk;
     if (t.gchunk) {
         const bk_u4_alias* k4 = reinterpret_cast<const bk_u4_alias*>(t.key);
-        uint32_t cb = e >> 3;
+        uint32_t cb = s.e >> 3;
         uint4 c = k4[cb];
         for (;;) {
-            if ((e >> 3) != cb) {
-                cb = e >> 3;
+            if ((s.e >> 3) != cb) {
+                cb = s.e >> 3;
                 c = k4[cb];
             }
-            const uint32_t q = (e >> 1) & 3u;
+            const uint32_t q = (s.e >> 1) & 3u;
             const uint32_t w = q == 0u ? c.x : q == 1u ? c.y : q == 2u ? c.z : c.w;
-            kk = (int16_t)(w >> (16u * (e & 1u)));
+            kk = (int16_t)(w >> (16u * (s.e & 1u)));
             if (kk == FS_UNUSED || kk == k) break;
-            if (kk == FS_DUMMY) freeslot = (int32_t)e;
-            if (left > 0u) {
-                --left;
-                ++e;
-            } else {
-                perturb >>= FS_SHIFT;
-                i = (i * 5u + 1u + (uint32_t)perturb) & mask;
-                e = i;
-                left = i + FS_PROBES <= mask ? FS_PROBES : 0u;
-            }
+            if (kk == FS_DUMMY) freeslot = (int32_t)s.e;
+            s.next(mask);
         }
-        e_out = e;
+        e_out = s.e;
         kk_out = kk;
         return;
     }
     for (;;) {
-        kk = t.at(e);
+        kk = t.at(s.e);
         if (kk == FS_UNUSED || kk == k) break;
-        if (kk == FS_DUMMY) freeslot = (int32_t)e;
-        if (left > 0u) {
-            --left;
-            ++e;
-        } else {
-            perturb >>= FS_SHIFT;
-            i = (i * 5u + 1u + (uint32_t)perturb) & mask;
-            e = i;
-            left = i + FS_PROBES <= mask ? FS_PROBES : 0u;
-        }
+        if (kk == FS_DUMMY) freeslot = (int32_t)s.e;
+        s.next(mask);
     }
-    e_out = e;
+    e_out = s.e;
     kk_out = kk;
 }
 
@@ -1734,21 +1721,28 @@ __host__ __device__ inline bool fs_op_nr(FsetRef t, int16_t k, bool add, uint64_
     return (uint64_t)*t.fill * 5 >= (uint64_t)mask * 3;
 }
 
-// set_table_resize after an add reached the threshold (set_add_entry's resize call)
-__host__ __device__ inline bool fs_resize_any(FsetRef t, int16_t* tmp, FsetRef ltmp) {
-    if (t.dirty) *t.dirty = ~0u;  // every slot is rewritten
-    const uint32_t minused = *t.used > 50000 ? *t.used * 2u : *t.used * 4u;
+// resize() and its result; in the diagnostic build (-DBK_SECTION_PROF, section slot 15)
+// also the wave cycles it took, counted by the first lane of each resize branch
+template <typename Resize>
+__host__ __device__ __forceinline__ bool fs_timed_resize(Resize resize) {
 #if defined(BK_SECTION_PROF) && defined(__HIP_DEVICE_COMPILE__)
-    // diagnostic (section slot 15): wave cycles in resizes, counted by the first lane of
-    // each resize branch
     const uint64_t rt0 = clock64();
-    const bool rok = ltmp.key && *t.used <= ltmp.cap ? fs_resize_lds(t, ltmp, minused) : fs_resize(t, tmp, minused);
+    const bool rok = resize();
     const uint64_t rex = __builtin_amdgcn_read_exec();
     if ((uint32_t)__lane_id() == (uint32_t)__builtin_ctzll(rex)) atomicAdd(&g_sections[15], clock64() - rt0);
     return rok;
 #else
-    return ltmp.key && *t.used <= ltmp.cap ? fs_resize_lds(t, ltmp, minused) : fs_resize(t, tmp, minused);
+    return resize();
 #endif
+}
+
+// set_table_resize after an add reached the threshold (set_add_entry's resize call)
+__host__ __device__ inline bool fs_resize_any(FsetRef t, int16_t* tmp, FsetRef ltmp) {
+    if (t.dirty) *t.dirty = ~0u;  // every slot is rewritten
+    const uint32_t minused = *t.used > 50000 ? *t.used * 2u : *t.used * 4u;
+    return fs_timed_resize([&] {
+        return ltmp.key && *t.used <= ltmp.cap ? fs_resize_lds(t, ltmp, minused) : fs_resize(t, tmp, minused);
+    });
 }
 
 __host__ __device__ inline bool fs_op_h(FsetRef t, int16_t* tmp, int16_t k, bool add, uint64_t h,
@@ -1813,15 +1807,25 @@ __host__ __device__ inline bool fs_place(FsetRef t, int16_t* tmp, const int32_t*
     return fs_place_pred(t, tmp, cells, n, addable);
 }
 
+// set.copy()'s size rule: the copy of a table with `used` active keys has newsize slots
+// (set_merge grows the fresh 8-slot table when (fill + other->used) * 5 >= mask * 3).  The
+// copy is slot-for-slot the source when the size is unchanged and the source has no
+// dummies (set_merge's same-size path)
+__host__ __device__ __forceinline__ uint32_t fs_copy_size(uint32_t used) {
+    uint32_t newsize = 8;
+    if (used * 5 >= 7u * 3u)
+        while (newsize <= used * 2) newsize <<= 1;
+    return newsize;
+}
+
 // set.copy() (make_new_set + set_merge into an empty set).  false: the copy's table
 // would not fit the storage (d left empty)
 __host__ __device__ inline bool fs_copy(FsetRef d, const int16_t* skey, uint32_t smask, uint32_t sfill,
                                         uint32_t sused) {
     fs_clear(d);
     if (sused == 0) return true;
-    if (sused * 5 >= 7u * 3u) {  // (fill + other->used) * 5 >= mask * 3 on the fresh table
-        uint32_t newsize = 8;
-        while (newsize <= sused * 2) newsize <<= 1;
+    const uint32_t newsize = fs_copy_size(sused);
+    if (newsize > 8u) {
         if (newsize > d.cap) return false;
         for (uint32_t i = 8; i < newsize; ++i) d.at(i) = FS_UNUSED;
         *d.mask = (uint16_t)(newsize - 1);
@@ -1839,6 +1843,19 @@ __host__ __device__ inline bool fs_copy(FsetRef d, const int16_t* skey, uint32_t
     return true;
 }
 
+// Bit s = 9 q + o of `real` (frontier_ops) is op o of the piece's cell q: its key, and
+// whether it adds (o = 1..4, the diagonals) or discards (the cell itself, the orthogonals)
+__device__ __forceinline__ int fs_decode_op(const int32_t (&cells)[5], int s, bool& add) {
+    // key offset + 21 of op o, 6 bits each: 0, -21, -19, 19, 21, -20, 20, -1, 1
+    constexpr uint64_t KD = (21ull << 0) | (0ull << 6) | (2ull << 12) | (40ull << 18) | (42ull << 24) |
+                            (1ull << 30) | (41ull << 36) | (20ull << 42) | (22ull << 48);
+    const int q = (s * 57) >> 9;  // s / 9 for s < 45
+    const int op = s - 9 * q;
+    const int cell = q == 0 ? cells[0] : q == 1 ? cells[1] : q == 2 ? cells[2] : q == 3 ? cells[3] : cells[4];
+    add = (unsigned)(op - 1) < 4u;
+    return cell + (int)((KD >> (6 * op)) & 63ull) - 21;
+}
+
 // Run the ops marked in `real` (frontier_ops) on table t, in order: one probe routine in
 // a per-lane loop, so a wave runs as many probe chains as its busiest lane has real ops
 // (typically ~10) instead of all 45.  false: table overflow.
@@ -1847,26 +1864,17 @@ __host__ __device__ inline bool fs_copy(FsetRef d, const int16_t* skey, uint32_t
 template <bool BATCH = true>
 __device__ __forceinline__ bool fs_run_ops(FsetRef t, int16_t* tmp, const int32_t (&cells)[5], uint64_t real,
                                            FsetRef ltmp = FsetRef{}) {
-    // key offset + 21 of op o, 6 bits each: 0, -21, -19, 19, 21, -20, 20, -1, 1
-    constexpr uint64_t KD = (21ull << 0) | (0ull << 6) | (2ull << 12) | (40ull << 18) | (42ull << 24) |
-                            (1ull << 30) | (41ull << 36) | (20ull << 42) | (22ull << 48);
-    auto key_of = [&](int s) {
-        const int q = (s * 57) >> 9;  // s / 9 for s < 45
-        const int op = s - 9 * q;
-        const int cell = q == 0 ? cells[0] : q == 1 ? cells[1] : q == 2 ? cells[2] : q == 3 ? cells[3] : cells[4];
-        return cell + (int)((KD >> (6 * op)) & 63ull) - 21;
-    };
     if constexpr (!BATCH) {
 #pragma unroll 1
         while (real) {
             const int s = (int)__builtin_ctzll(real);
             real &= real - 1ull;
-            const int op = s - 9 * ((s * 57) >> 9);
-            const int key = key_of(s);
+            bool add;
+            const int key = fs_decode_op(cells, s, add);
             // (a wave-parallel version -- op hashes loaded up front, one lane per slot of
             // the first linear probe run, ballot for the stop -- measured 3 % slower:
             // most chains stop at their first slot; profiles/r06/sweeps/r06w)
-            if (!fs_op_h(t, tmp, (int16_t)key, (unsigned)(op - 1) < 4u, t.hash[key], ltmp)) return false;
+            if (!fs_op_h(t, tmp, (int16_t)key, add, t.hash[key], ltmp)) return false;
         }
         return true;
     }
@@ -1882,12 +1890,12 @@ __device__ __forceinline__ bool fs_run_ops(FsetRef t, int16_t* tmp, const int32_
         while (real && !need) {
             const int s = (int)__builtin_ctzll(real);
             real &= real - 1ull;
-            const int op = s - 9 * ((s * 57) >> 9);
-            const int key = key_of(s);
+            bool add;
+            const int key = fs_decode_op(cells, s, add);
             // (loading the next ops' hashes ahead, 3 or 6 in flight, measured slower:
             // 34.2 -> 33.6 M frontier-order playouts/s, profiles/r05/sweeps/r05g)
             const uint64_t h = t.hash[key];
-            need = fs_op_nr(t, (int16_t)key, (unsigned)(op - 1) < 4u, h);
+            need = fs_op_nr(t, (int16_t)key, add, h);
         }
         if (need && !fs_resize_any(t, tmp, ltmp)) {
             ok = false;  // the table outgrew this storage: the caller starts over elsewhere
@@ -1910,6 +1918,18 @@ __device__ __forceinline__ FsetRef lds_tmp(int16_t* ltk, uint32_t keys) {
     return r;
 }
 
+// 8-slot chunk i of a table to / from a lane's LDS stage column lw ([slot pair][lane]:
+// dword j of the table at lw[j * WAVE])
+__device__ __forceinline__ void stage_put(bk_u32_alias* lw, int i, const uint4& v) {
+    lw[(4 * i + 0) * WAVE] = v.x;
+    lw[(4 * i + 1) * WAVE] = v.y;
+    lw[(4 * i + 2) * WAVE] = v.z;
+    lw[(4 * i + 3) * WAVE] = v.w;
+}
+__device__ __forceinline__ uint4 stage_get(const bk_u32_alias* lw, int i) {
+    return make_uint4(lw[(4 * i + 0) * WAVE], lw[(4 * i + 1) * WAVE], lw[(4 * i + 2) * WAVE], lw[(4 * i + 3) * WAVE]);
+}
+
 // per-lane frontier record in the rollout kernel: the tables plus resize scratch.
 // padded to whole 128-byte lines, so each player's table starts on a line and a table of
 // <= 64 slots is ONE line (2,592 -> 2,688 bytes; see the slab's padding)
@@ -1918,22 +1938,6 @@ struct FsLane {
     int16_t tmp[BK_FSET_SLOTS];
     int16_t pad[48];  // 2592 -> 2688 bytes
 };
-
-// update_frontier_after_move (engine/board.py:315-367) of player p's table in fl for a
-// piece at cells[0..n): the ops marked in `real` (frontier_ops).  A table of < STAGE
-// slots is staged in LDS so the probe chains wait on LDS, not L2/HBM: lk = this lane's dword of [slot pair][lane] (slots 2j, 2j + 1 in dword j *
-// WAVE): one ds_write_b32 / ds_read_b32 per slot pair, and a probe of ANY slot by each
-// lane hits bank `lane` (conflict-free).  A larger table (or a move that grows one past
-// the stage) is updated in place.  false: table overflow.
-// fs_copy_dev's size rule: the copy of a table with `used` active keys has newsize
-// slots; the copy is slot-for-slot the source when the size is unchanged and the source
-// has no dummies (set_merge's same-size path)
-__device__ __forceinline__ uint32_t fs_copy_size(uint32_t used) {
-    uint32_t newsize = 8;
-    if (used * 5 >= 7u * 3u)
-        while (newsize <= used * 2) newsize <<= 1;
-    return newsize;
-}
 
 // Board.copy() of table q of fl in place (the copy replaces the table): the source keys
 // go to fl->tmp, the destination is cleared and the keys re-inserted in slot order with
@@ -1952,34 +1956,28 @@ __device__ __forceinline__ bool fs_recopy_global(FsLane* fl, int q, const uint64
     bk_u4_alias* t4 = reinterpret_cast<bk_u4_alias*>(fl->tmp);
 #pragma unroll 1
     for (uint32_t i = 0; i <= smask / 8; ++i) t4[i] = k4[i];
-    const uint4 unused = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-#pragma unroll 1
-    for (uint32_t i = 0; i < newsize / 8; ++i) k4[i] = unused;
-    s->mask[q] = (uint16_t)(newsize - 1);
-    s->fill[q] = (uint16_t)sused;
-    s->used[q] = (uint16_t)sused;
+    fs_fresh_table(k4, newsize, sused, &s->mask[q], &s->fill[q], &s->used[q]);
     SlotBits o;
 #pragma unroll 1
-    for (uint32_t i = 0; i <= smask / 8; ++i) {
-        const uint4 v = t4[i];
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int16_t k = (int16_t)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu));
-            if (k >= 0) s->key[q][fs_clean_slot(htab[k], newsize - 1, o)] = k;
-        }
-    }
+    for (uint32_t i = 0; i <= smask / 8; ++i) fs_reinsert_chunk(t4[i], s->key[q], newsize - 1, htab, o);
     return true;
 }
 
+struct NoMark {  // (no section marks)
+    __device__ __forceinline__ void operator()(int) const {}
+};
+
+// update_frontier_after_move (engine/board.py:315-367) of player p's table in fl for a
+// piece at cells[0..n): the ops marked in `real` (frontier_ops).  A table of < STAGE
+// slots is staged in LDS so the probe chains wait on LDS, not L2/HBM: lk = this lane's
+// dword of [slot pair][lane] (slots 2j, 2j + 1 in dword j * WAVE): one ds_write_b32 /
+// ds_read_b32 per slot pair, and a probe of ANY slot by each lane hits bank `lane`
+// (conflict-free).  A larger table (or a move that grows one past the stage) is updated
+// in place.  false: table overflow.
 // RECOPY: the table after the ops is replaced by its Board.copy() (MCTSNode boards are
 // copies of copies, mcts_agent.py:113-145): from the LDS stage, the keys are re-inserted
 // straight into the global table (slots from a register bitmap), so the copy costs no
 // second record and no reads of global memory.
-struct NoMark {
-    __device__ __forceinline__ void operator()(int) const {}
-};
-
 // mark(i): section boundaries for the diagnostic build (-DBK_SECTION_PROF)
 // hdr: player p's (mask, fill, used) when kept outside the record (the rollout slab);
 // nullptr: the record's own header
@@ -2008,13 +2006,7 @@ __device__ __forceinline__ bool place_frontier(FsLane* fl, int p, int16_t* lk, c
     if (STAGE > 0 && gmask < (uint32_t)STAGE) {
 #pragma unroll
         for (int i = 0; i < STAGE / 8; ++i) {
-            if ((uint32_t)(8 * i) <= gmask) {
-                const uint4 v = EAGER ? pre[EAGER ? i : 0] : src4[i];
-                lw[(4 * i + 0) * WAVE] = v.x;
-                lw[(4 * i + 1) * WAVE] = v.y;
-                lw[(4 * i + 2) * WAVE] = v.z;
-                lw[(4 * i + 3) * WAVE] = v.w;
-            }
+            if ((uint32_t)(8 * i) <= gmask) stage_put(lw, i, EAGER ? pre[EAGER ? i : 0] : src4[i]);
         }
         const uint16_t m0 = (uint16_t)gmask, f0 = *hf, u0 = *hu;
         uint16_t m = m0, f = f0, u = u0;
@@ -2029,9 +2021,7 @@ __device__ __forceinline__ bool place_frontier(FsLane* fl, int p, int16_t* lk, c
             if (!RECOPY || (newsize - 1 == m && f == u)) {  // (a copy of a clean table is the table)
 #pragma unroll
                 for (int i = 0; i < STAGE / 8; ++i) {
-                    if ((uint32_t)(8 * i) <= m && ((dirty >> i) & 1u))
-                        dst4[i] = make_uint4(lw[(4 * i + 0) * WAVE], lw[(4 * i + 1) * WAVE],
-                                             lw[(4 * i + 2) * WAVE], lw[(4 * i + 3) * WAVE]);
+                    if ((uint32_t)(8 * i) <= m && ((dirty >> i) & 1u)) dst4[i] = stage_get(lw, i);
                 }
                 if (m != m0) *hm = m;
                 if (f != f0) *hf = f;
@@ -2039,19 +2029,10 @@ __device__ __forceinline__ bool place_frontier(FsLane* fl, int p, int16_t* lk, c
                 return true;
             }
             // the copy: newsize <= 2 * STAGE <= BK_FSET_SLOTS (u < STAGE * 3 / 5)
-            const uint4 unused = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-#pragma unroll 1
-            for (uint32_t i = 0; i < newsize / 8; ++i) dst4[i] = unused;
-            *hm = (uint16_t)(newsize - 1); *hf = u; *hu = u;
+            fs_fresh_table(dst4, newsize, u, hm, hf, hu);
             SlotBits o;
-            int16_t* dk = gfs->key[p];
 #pragma unroll 1
-            for (uint32_t j = 0; j <= m / 2; ++j) {
-                const uint32_t w = lw[j * WAVE];
-                const int16_t k0 = (int16_t)(w & 0xFFFFu), k1 = (int16_t)(w >> 16);
-                if (k0 >= 0) dk[fs_clean_slot(htab[k0], newsize - 1, o)] = k0;
-                if (k1 >= 0) dk[fs_clean_slot(htab[k1], newsize - 1, o)] = k1;
-            }
+            for (uint32_t j = 0; j <= m / 2; ++j) fs_reinsert_pair(lw[j * WAVE], gfs->key[p], newsize - 1, htab, o);
             return true;
         }
     }
@@ -2118,25 +2099,16 @@ struct FsMix {
 // fs_op_nr (fs_probe's sequence) on a lane's own kind of table
 __device__ __forceinline__ bool fs_op_mix(FsMix& t, int16_t k, bool add, uint64_t h) {
     const uint32_t mask = t.m;
-    uint64_t perturb = h;
-    uint32_t i = (uint32_t)h & mask, e = i;
-    uint32_t left = i + FS_PROBES <= mask ? FS_PROBES : 0u;
+    FsProbeSeq s(h, mask);
     int32_t freeslot = -1;
     int16_t kk;
     for (;;) {
-        kk = *t.slot(e);
+        kk = *t.slot(s.e);
         if (kk == FS_UNUSED || kk == k) break;
-        if (kk == FS_DUMMY) freeslot = (int32_t)e;
-        if (left > 0u) {
-            --left;
-            ++e;
-        } else {
-            perturb >>= FS_SHIFT;
-            i = (i * 5u + 1u + (uint32_t)perturb) & mask;
-            e = i;
-            left = i + FS_PROBES <= mask ? FS_PROBES : 0u;
-        }
+        if (kk == FS_DUMMY) freeslot = (int32_t)s.e;
+        s.next(mask);
     }
+    const uint32_t e = s.e;
     if (kk == k) {  // present: discard leaves a dummy, add is a no-op
         if (!add) {
             t.put(e, FS_DUMMY);
@@ -2185,8 +2157,6 @@ __device__ __forceinline__ bool fs_resize_mix(FsMix& t, int16_t* ltk, const uint
 template <int STAGE>
 __device__ __forceinline__ bool fs_run_ops_mix(FsMix& t, int16_t* ltk, const uint64_t* htab,
                                                const int32_t (&cells)[5], uint64_t real, const uint4* lmp) {
-    constexpr uint64_t KD = (21ull << 0) | (0ull << 6) | (2ull << 12) | (40ull << 18) | (42ull << 24) |
-                            (1ull << 30) | (41ull << 36) | (20ull << 42) | (22ull << 48);  // fs_run_ops
     const uint64_t real0 = real;
     const uint16_t m0 = t.m, f0 = t.f, u0 = t.u;
     bool ok = true;
@@ -2197,22 +2167,12 @@ __device__ __forceinline__ bool fs_run_ops_mix(FsMix& t, int16_t* ltk, const uin
         while (real && !need) {
             const int s = (int)__builtin_ctzll(real);
             real &= real - 1ull;
-            const int q = (s * 57) >> 9;  // s / 9 for s < 45
-            const int op = s - 9 * q;
-            const int cell = q == 0 ? cells[0] : q == 1 ? cells[1] : q == 2 ? cells[2] : q == 3 ? cells[3] : cells[4];
-            const int key = cell + (int)((KD >> (6 * op)) & 63ull) - 21;
-            need = fs_op_mix(t, (int16_t)key, (unsigned)(op - 1) < 4u, htab[key]);
+            bool add;
+            const int key = fs_decode_op(cells, s, add);
+            need = fs_op_mix(t, (int16_t)key, add, htab[key]);
         }
         if (need) {  // the resizes of a round run together (fs_run_ops), each lane with its own scratch
-#ifdef BK_SECTION_PROF
-            const uint64_t rt0 = clock64();  // (section slot 15, as fs_resize_any)
-            const bool rok = fs_resize_mix<STAGE>(t, ltk, htab);
-            const uint64_t rex = __builtin_amdgcn_read_exec();
-            if ((uint32_t)__lane_id() == (uint32_t)__builtin_ctzll(rex)) atomicAdd(&g_sections[15], clock64() - rt0);
-#else
-            const bool rok = fs_resize_mix<STAGE>(t, ltk, htab);
-#endif
-            if (!rok) {
+            if (!fs_timed_resize([&] { return fs_resize_mix<STAGE>(t, ltk, htab); })) {
                 if (t.glob) {
                     ok = false;
                     real = 0;
@@ -2255,12 +2215,7 @@ __device__ __forceinline__ bool place_frontier_onepass(FsLane* fl, int p, int16_
     if (!t.glob) {
 #pragma unroll
         for (int i = 0; i < STAGE / 8; ++i) {
-            if ((uint32_t)(8 * i) <= (uint32_t)m0) {
-                lw[(4 * i + 0) * WAVE] = pre[i].x;
-                lw[(4 * i + 1) * WAVE] = pre[i].y;
-                lw[(4 * i + 2) * WAVE] = pre[i].z;
-                lw[(4 * i + 3) * WAVE] = pre[i].w;
-            }
+            if ((uint32_t)(8 * i) <= (uint32_t)m0) stage_put(lw, i, pre[i]);
         }
     }
     mark(8);
@@ -2270,9 +2225,7 @@ __device__ __forceinline__ bool place_frontier_onepass(FsLane* fl, int p, int16_
         bk_u4_alias* dst4 = reinterpret_cast<bk_u4_alias*>(gfs->key[p]);
 #pragma unroll
         for (int i = 0; i < STAGE / 8; ++i) {
-            if ((uint32_t)(8 * i) <= (uint32_t)t.m && ((t.dirty >> i) & 1u))
-                dst4[i] = make_uint4(lw[(4 * i + 0) * WAVE], lw[(4 * i + 1) * WAVE], lw[(4 * i + 2) * WAVE],
-                                     lw[(4 * i + 3) * WAVE]);
+            if ((uint32_t)(8 * i) <= (uint32_t)t.m && ((t.dirty >> i) & 1u)) dst4[i] = stage_get(lw, i);
         }
     }
     if (t.m != m0) hdr[0] = t.m;
@@ -2331,22 +2284,11 @@ __device__ __forceinline__ bool place_frontier_dma(FsLane* fl, int p, int16_t* s
             return true;
         }
         // (never in place: the copy reads the stage while it rewrites the table)
-        const uint4 unused = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-#pragma unroll 1
-        for (uint32_t i = 0; i < newsize / 8; ++i) dst4[i] = unused;
-        gfs->mask[p] = (uint16_t)(newsize - 1); gfs->fill[p] = u; gfs->used[p] = u;
+        fs_fresh_table(dst4, newsize, u, &gfs->mask[p], &gfs->fill[p], &gfs->used[p]);
         SlotBits o;
-        int16_t* dk = gfs->key[p];
 #pragma unroll 1
-        for (uint32_t i = 0; i <= m; i += 8) {
-            const uint4 v = src4[(i >> 4) * RUN_U4 + ((i >> 3) & 1u)];
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int16_t k = (int16_t)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu));
-                if (k >= 0) dk[fs_clean_slot(htab[k], newsize - 1, o)] = k;
-            }
-        }
+        for (uint32_t i = 0; i <= m; i += 8)
+            fs_reinsert_chunk(src4[(i >> 4) * RUN_U4 + ((i >> 3) & 1u)], gfs->key[p], newsize - 1, htab, o);
         return true;
     }
     if (inplace) return false;  // (the ops ran on the table: past its 256 slots)
@@ -2506,29 +2448,9 @@ __device__ __forceinline__ uint32_t heur_pass_a(const Planes& P, uint32_t avail,
 
 // legal anchor rows of orientation gs (per lane) from the {B, C} rows in LDS
 __device__ __forceinline__ void lane_ok_rows(int gs, const uint2* rows, uint32_t (&ok)[20]) {
-    const uint32_t info = kInfo[gs];
-    const int n = (int)((info >> 8) & 0xFFu);
-    const int rlim = 20 - (int)((info >> 16) & 0xFFu);
-    const uint2* base[5];
-    uint32_t sh[5];
+    const LocCells lc = locate_cells(gs, rows);
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const uint32_t cell = kCells[gs][k < n ? k : 0];
-        base[k] = rows + (cell >> 8) * WAVE;
-        sh[k] = cell & 0xFFu;
-    }
-#pragma unroll
-    for (int r = 0; r < 20; ++r) {
-        const int rr = r < rlim ? r : rlim;
-        uint2 v[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) v[k] = base[k][rr * WAVE];
-        uint32_t ab = BITOP3(v[0].x >> sh[0], v[1].x >> sh[1], v[2].x >> sh[2], LUT_OR3);
-        uint32_t ac = BITOP3(v[0].y >> sh[0], v[1].y >> sh[1], v[2].y >> sh[2], LUT_OR3);
-        ab = BITOP3(ab, v[3].x >> sh[3], v[4].x >> sh[4], LUT_OR3);
-        ac = BITOP3(ac, v[3].y >> sh[3], v[4].y >> sh[4], LUT_OR3);
-        ok[r] = r <= rlim ? (ac & ~ab) : 0u;
-    }
+    for (int r = 0; r < 20; ++r) ok[r] = anchor_row(lc, r);
 }
 
 __device__ __forceinline__ double lane_orient_sum(int gs, const uint32_t (&ok)[20], const uint2* rows,
@@ -2618,7 +2540,7 @@ __device__ __forceinline__ void heur_walk_frontier(int gs, const uint32_t (&ok)[
         const uint32_t w[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-            const int f = (int)(int16_t)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu));
+            const int f = fs_key16(w, j);
             if (found_r >= 0 || f < 0 || b0 + j > mask) continue;
             const int fr = f / 20, fc = f - 20 * fr;
 #pragma unroll
@@ -2752,9 +2674,37 @@ __device__ __forceinline__ void store_state(const RolloutArgs& a, const Game& g,
     o->reserved[1] = a.seat_masks ? g.passes0 + (uint32_t)g.passes : 0u;
 }
 
-// player p's table header in the rollout slab (frontier order, SLAB_HDR_BASE)
+// player p's table header in the rollout slab (frontier order): (mask, fill, used) as three
+// uint16, the four players' back to back in the six dwords from SLAB_HDR_BASE
 __device__ __forceinline__ uint16_t* slab_hdr(const Slab& slab, int p) {
     return reinterpret_cast<uint16_t*>(&slab.word(SLAB_HDR_BASE)) + 3 * p;
+}
+
+// the headers of a game's four tables, unpacked: from a record's 32-byte tail (t0, t1 =
+// mask[4] fill[4] used[4] reserved[4], uint16 each), and to / from slab_hdr's six dwords
+struct FsetHdrs {
+    uint32_t mask[4], fill[4], used[4];
+};
+__device__ __forceinline__ FsetHdrs fset_tail_unpack(const uint4& t0, const uint4& t1) {
+    return FsetHdrs{{t0.x & 0xFFFFu, t0.x >> 16, t0.y & 0xFFFFu, t0.y >> 16},
+                    {t0.z & 0xFFFFu, t0.z >> 16, t0.w & 0xFFFFu, t0.w >> 16},
+                    {t1.x & 0xFFFFu, t1.x >> 16, t1.y & 0xFFFFu, t1.y >> 16}};
+}
+__device__ __forceinline__ void slab_hdr_store(const Slab& slab, const FsetHdrs& h) {
+    slab.word(SLAB_HDR_BASE + 0) = h.mask[0] | (h.fill[0] << 16);
+    slab.word(SLAB_HDR_BASE + 1) = h.used[0] | (h.mask[1] << 16);
+    slab.word(SLAB_HDR_BASE + 2) = h.fill[1] | (h.used[1] << 16);
+    slab.word(SLAB_HDR_BASE + 3) = h.mask[2] | (h.fill[2] << 16);
+    slab.word(SLAB_HDR_BASE + 4) = h.used[2] | (h.mask[3] << 16);
+    slab.word(SLAB_HDR_BASE + 5) = h.fill[3] | (h.used[3] << 16);
+}
+__device__ __forceinline__ FsetHdrs slab_hdr_load(const Slab& slab) {
+    uint32_t h[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) h[i] = slab.word(SLAB_HDR_BASE + i);
+    return FsetHdrs{{h[0] & 0xFFFFu, h[1] >> 16, h[3] & 0xFFFFu, h[4] >> 16},
+                    {h[0] >> 16, h[2] & 0xFFFFu, h[3] >> 16, h[5] & 0xFFFFu},
+                    {h[1] & 0xFFFFu, h[2] >> 16, h[4] & 0xFFFFu, h[5] >> 16}};
 }
 
 // k_rollout_fr keeps, per player, 128 bits next to the game: bit s is set iff key[s] >= 0,
@@ -2778,7 +2728,7 @@ __device__ __forceinline__ void live_chunk(const uint4& v, uint32_t i, uint4& l)
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
     uint32_t dead = 0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) dead |= (((w[j] >> 15) & 1u) | ((w[j] >> 30) & 2u)) << (2 * j);
+    for (int j = 0; j < 4; ++j) dead |= fs_dead2(w[j]) << (2 * j);
     const uint32_t b = (~dead & 0xFFu) << ((i & 3u) * 8u), wd = i >> 2;
     l.x |= wd == 0u ? b : 0u;
     l.y |= wd == 1u ? b : 0u;
@@ -2802,101 +2752,60 @@ __device__ __forceinline__ void init_live_masks(const bk_fset* fs, const Slab& s
     }
 }
 
-// a plain copy of the four tables: slots 0..mask of each (the rest is never read) and
-// the counters, as uint4
-__device__ __forceinline__ void copy_fset(bk_fset* dst, const bk_fset* src) {
+// slots 0..mask of table q (the rest is never read) from src to dst, 8 slots per uint4;
+// chunk(i, v) sees each chunk i copied
+template <typename Chunk>
+__device__ __forceinline__ void copy_fset_table(bk_fset* dst, const bk_fset* src, int q, uint32_t mask, Chunk chunk) {
     static_assert(sizeof(bk_fset) % 16 == 0 && BK_FSET_SLOTS % 8 == 0, "bk_fset is copied as uint4");
+    const bk_u4_alias* s4 = reinterpret_cast<const bk_u4_alias*>(src->key[q]);
+    bk_u4_alias* d4 = reinterpret_cast<bk_u4_alias*>(dst->key[q]);
+    const uint32_t nv = (mask + 1u) / 8u;
+#pragma unroll 2
+    for (uint32_t i = 0; i < nv; ++i) {
+        const uint4 v = s4[i];
+        d4[i] = v;
+        chunk(i, v);
+    }
+}
+
+// a plain copy of the four tables and the counters
+__device__ __forceinline__ void copy_fset(bk_fset* dst, const bk_fset* src) {
     const bk_u4_alias* tail_s = reinterpret_cast<const bk_u4_alias*>(&src->mask[0]);
     bk_u4_alias* tail_d = reinterpret_cast<bk_u4_alias*>(&dst->mask[0]);
-    const uint4 t0 = tail_s[0], t1 = tail_s[1];  // mask[4] fill[4] used[4] reserved[4]
+    const uint4 t0 = tail_s[0], t1 = tail_s[1];
     tail_d[0] = t0;
     tail_d[1] = t1;
-    const uint32_t masks[4] = {t0.x & 0xFFFFu, t0.x >> 16, t0.y & 0xFFFFu, t0.y >> 16};
+    const FsetHdrs h = fset_tail_unpack(t0, t1);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const bk_u4_alias* s4 = reinterpret_cast<const bk_u4_alias*>(src->key[q]);
-        bk_u4_alias* d4 = reinterpret_cast<bk_u4_alias*>(dst->key[q]);
-        const int nv = (int)(masks[q] + 1u) / 8;  // 8 slots per uint4
-#pragma unroll 2
-        for (int i = 0; i < nv; ++i) d4[i] = s4[i];
-    }
+    for (int q = 0; q < 4; ++q) copy_fset_table(dst, src, q, h.mask[q], [](uint32_t, const uint4&) {});
 }
 
 // copy_fset with the headers (mask, fill, used) to / from the rollout slab instead of the
-// record's header line (the record's own header is not kept up to date)
-__device__ __forceinline__ void copy_fset_in(bk_fset* dst, const Slab& slab, const bk_fset* src) {
+// record's header line (the record's own header is not kept up to date).  Also builds the
+// tables' live-slot masks lm[0..3] (live_masks) from the words it copies: a pass of its own
+// over the copied tables waited for 64 more loads at the start of every game (-1 % of
+// k_rollout_fr's launch, profiles/r09/sweeps/r09a).  A caller that keeps no masks passes a
+// local array, and the compiler drops them
+__device__ __forceinline__ void copy_fset_in(bk_fset* dst, const Slab& slab, const bk_fset* src, uint4* lm) {
     const bk_u4_alias* tail_s = reinterpret_cast<const bk_u4_alias*>(&src->mask[0]);
-    const uint4 t0 = tail_s[0], t1 = tail_s[1];  // mask[4] fill[4] used[4] reserved[4]
-    const uint32_t masks[4] = {t0.x & 0xFFFFu, t0.x >> 16, t0.y & 0xFFFFu, t0.y >> 16};
-    const uint32_t fills[4] = {t0.z & 0xFFFFu, t0.z >> 16, t0.w & 0xFFFFu, t0.w >> 16};
-    const uint32_t useds[4] = {t1.x & 0xFFFFu, t1.x >> 16, t1.y & 0xFFFFu, t1.y >> 16};
-    // (mask, fill, used) x 4 as 6 dwords
-    slab.word(SLAB_HDR_BASE + 0) = masks[0] | (fills[0] << 16);
-    slab.word(SLAB_HDR_BASE + 1) = useds[0] | (masks[1] << 16);
-    slab.word(SLAB_HDR_BASE + 2) = fills[1] | (useds[1] << 16);
-    slab.word(SLAB_HDR_BASE + 3) = masks[2] | (fills[2] << 16);
-    slab.word(SLAB_HDR_BASE + 4) = useds[2] | (masks[3] << 16);
-    slab.word(SLAB_HDR_BASE + 5) = fills[3] | (useds[3] << 16);
+    const FsetHdrs h = fset_tail_unpack(tail_s[0], tail_s[1]);
+    slab_hdr_store(slab, h);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const bk_u4_alias* s4 = reinterpret_cast<const bk_u4_alias*>(src->key[q]);
-        bk_u4_alias* d4 = reinterpret_cast<bk_u4_alias*>(dst->key[q]);
-        const int nv = (int)(masks[q] + 1u) / 8;  // 8 slots per uint4
-#pragma unroll 2
-        for (int i = 0; i < nv; ++i) d4[i] = s4[i];
-    }
-}
-
-// copy_fset_in that also builds the tables' live-slot masks lm[0..3] (live_masks) from the
-// words it copies: a pass of its own over the copied tables waited for 64 more loads at the
-// start of every game (-1 % of k_rollout_fr's launch, profiles/r09/sweeps/r09a)
-__device__ __forceinline__ void copy_fset_in_live(bk_fset* dst, const Slab& slab, const bk_fset* src, uint4* lm) {
-    const bk_u4_alias* tail_s = reinterpret_cast<const bk_u4_alias*>(&src->mask[0]);
-    const uint4 t0 = tail_s[0], t1 = tail_s[1];  // mask[4] fill[4] used[4] reserved[4]
-    const uint32_t masks[4] = {t0.x & 0xFFFFu, t0.x >> 16, t0.y & 0xFFFFu, t0.y >> 16};
-    const uint32_t fills[4] = {t0.z & 0xFFFFu, t0.z >> 16, t0.w & 0xFFFFu, t0.w >> 16};
-    const uint32_t useds[4] = {t1.x & 0xFFFFu, t1.x >> 16, t1.y & 0xFFFFu, t1.y >> 16};
-    slab.word(SLAB_HDR_BASE + 0) = masks[0] | (fills[0] << 16);
-    slab.word(SLAB_HDR_BASE + 1) = useds[0] | (masks[1] << 16);
-    slab.word(SLAB_HDR_BASE + 2) = fills[1] | (useds[1] << 16);
-    slab.word(SLAB_HDR_BASE + 3) = masks[2] | (fills[2] << 16);
-    slab.word(SLAB_HDR_BASE + 4) = useds[2] | (masks[3] << 16);
-    slab.word(SLAB_HDR_BASE + 5) = fills[3] | (useds[3] << 16);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const bk_u4_alias* s4 = reinterpret_cast<const bk_u4_alias*>(src->key[q]);
-        bk_u4_alias* d4 = reinterpret_cast<bk_u4_alias*>(dst->key[q]);
-        const uint32_t nv = (masks[q] + 1u) / 8u;  // 8 slots per uint4
         uint4 l = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll 2
-        for (uint32_t i = 0; i < nv; ++i) {
-            const uint4 v = s4[i];
-            d4[i] = v;
-            live_chunk(v, i, l);
-        }
+        copy_fset_table(dst, src, q, h.mask[q], [&](uint32_t i, const uint4& v) { live_chunk(v, i, l); });
         lm[q] = l;
     }
 }
 
 __device__ __forceinline__ void copy_fset_out(bk_fset* dst, const bk_fset* src, const Slab& slab) {
-    uint32_t h[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) h[i] = slab.word(SLAB_HDR_BASE + i);
-    const uint32_t masks[4] = {h[0] & 0xFFFFu, h[1] >> 16, h[3] & 0xFFFFu, h[4] >> 16};
-    const uint32_t fills[4] = {h[0] >> 16, h[2] & 0xFFFFu, h[3] >> 16, h[5] & 0xFFFFu};
-    const uint32_t useds[4] = {h[1] & 0xFFFFu, h[2] >> 16, h[4] & 0xFFFFu, h[5] >> 16};
+    const FsetHdrs h = slab_hdr_load(slab);
     bk_u4_alias* tail_d = reinterpret_cast<bk_u4_alias*>(&dst->mask[0]);
-    tail_d[0] = make_uint4(masks[0] | (masks[1] << 16), masks[2] | (masks[3] << 16), fills[0] | (fills[1] << 16),
-                           fills[2] | (fills[3] << 16));
-    tail_d[1] = make_uint4(useds[0] | (useds[1] << 16), useds[2] | (useds[3] << 16), 0u, 0u);
+    tail_d[0] = make_uint4(h.mask[0] | (h.mask[1] << 16), h.mask[2] | (h.mask[3] << 16), h.fill[0] | (h.fill[1] << 16),
+                           h.fill[2] | (h.fill[3] << 16));
+    tail_d[1] = make_uint4(h.used[0] | (h.used[1] << 16), h.used[2] | (h.used[3] << 16), 0u, 0u);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const bk_u4_alias* s4 = reinterpret_cast<const bk_u4_alias*>(src->key[q]);
-        bk_u4_alias* d4 = reinterpret_cast<bk_u4_alias*>(dst->key[q]);
-        const int nv = (int)(masks[q] + 1u) / 8;
-#pragma unroll 2
-        for (int i = 0; i < nv; ++i) d4[i] = s4[i];
-    }
+    for (int q = 0; q < 4; ++q) copy_fset_table(dst, src, q, h.mask[q], [](uint32_t, const uint4&) {});
 }
 
 // fs_copy of table q on the device, as uint4 rows (8 slots each): the same-shape case
@@ -2904,9 +2813,7 @@ __device__ __forceinline__ void copy_fset_out(bk_fset* dst, const bk_fset* src, 
 // load.  Equal to fs_copy slot for slot.
 __device__ __forceinline__ bool fs_copy_dev(bk_fset* d, int q, const bk_fset* s, const uint64_t* htab) {
     const uint32_t smask = s->mask[q], sfill = s->fill[q], sused = s->used[q];
-    uint32_t newsize = 8;
-    if (sused * 5 >= 7u * 3u)
-        while (newsize <= sused * 2) newsize <<= 1;
+    const uint32_t newsize = fs_copy_size(sused);
     bk_u4_alias* d4 = reinterpret_cast<bk_u4_alias*>(d->key[q]);
     const bk_u4_alias* s4 = reinterpret_cast<const bk_u4_alias*>(s->key[q]);
     if (newsize > BK_FSET_SLOTS) {
@@ -2932,8 +2839,8 @@ __device__ __forceinline__ bool fs_copy_dev(bk_fset* d, int q, const bk_fset* s,
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int16_t k = (int16_t)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu));
-            if (k >= 0) fs_insert_clean(t, newsize - 1, k);
+            const int k = fs_key16(w, j);
+            if (k >= 0) fs_insert_clean(t, newsize - 1, (int16_t)k);
         }
     }
     return true;
@@ -3073,10 +2980,8 @@ __device__ __forceinline__ void start_game(const RolloutArgs& a, Game& g, const 
             }
             if constexpr (LIVE) init_live_masks(d, slab, lm);
         } else {
-            if constexpr (LIVE)
-                copy_fset_in_live(&a.fslab[slot].s, slab, a.root_sets + ri, lm);
-            else
-                copy_fset_in(&a.fslab[slot].s, slab, a.root_sets + ri);
+            uint4 nolm[4];  // (not LIVE: no masks are kept)
+            copy_fset_in(&a.fslab[slot].s, slab, a.root_sets + ri, LIVE ? lm : nolm);
         }
     }
     g.hmask = a.seat_masks ? (a.seat_masks[pid] & 0xFu) : (uint32_t)a.cfg.heuristic_seats;
@@ -5092,24 +4997,7 @@ __device__ __forceinline__ void coop_list_moves(uint16_t* ml, uint32_t idx, uint
 // wave-uniform -- instead of every lane computing all 20 rows (100 LDS reads and ~240
 // VALU per lane).  All 64 lanes must be active (the cooperative kernels' uniform flow).
 __device__ __forceinline__ void coop_ok_rows(int gs, const uint2* rows, int lane, uint32_t (&ok)[20]) {
-    const uint32_t info = kInfo[gs];
-    const int n = (int)((info >> 8) & 0xFFu);
-    const int rlim = 20 - (int)((info >> 16) & 0xFFu);
-    const int r = lane < 20 ? lane : 0;
-    const int rr = r < rlim ? r : rlim;
-    uint2 v[5];
-    uint32_t sh[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const uint32_t cell = kCells[gs][k < n ? k : 0];
-        sh[k] = cell & 0xFFu;
-        v[k] = rows[(rr + (int)(cell >> 8)) * WAVE];
-    }
-    uint32_t ab = BITOP3(v[0].x >> sh[0], v[1].x >> sh[1], v[2].x >> sh[2], LUT_OR3);
-    uint32_t ac = BITOP3(v[0].y >> sh[0], v[1].y >> sh[1], v[2].y >> sh[2], LUT_OR3);
-    ab = BITOP3(ab, v[3].x >> sh[3], v[4].x >> sh[4], LUT_OR3);
-    ac = BITOP3(ac, v[3].y >> sh[3], v[4].y >> sh[4], LUT_OR3);
-    const uint32_t mine = r <= rlim ? (ac & ~ab) : 0u;
+    const uint32_t mine = anchor_row(locate_cells(gs, rows), lane < 20 ? lane : 0);
 #pragma unroll
     for (int q = 0; q < 20; ++q) ok[q] = (uint32_t)__builtin_amdgcn_readlane((int)mine, q);
 }
