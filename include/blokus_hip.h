@@ -348,10 +348,14 @@ int bk_mt_cursor_init(uint32_t seed, uint32_t* out4);
  * random()*0.1, random() being CPython random.Random's genrand_res53 from the state
  * mt_state[i] (625 words: random.getstate()[1]); a NaN base[i] means reward 0.0 with no
  * draw (empty cached legal list, fast_mcts_agent.py:255).  mt_state is in/out: the
- * advanced state is written back.  Results per game in out; visits_out (optional, may
+ * advanced state is written back.  mt_state[i][624], the position, may be any value
+ * 0..624, odd ones included (a random() then takes its two words from either side of a
+ * twist).  Results per game in out; visits_out (optional, may
  * be NULL) receives every root child's visit count at its legal index (flat, by
- * legal_offset; 0 = never expanded).  Replaces the per-iteration
- * Python loop of FastMCTSAgent.think (fast_mcts_agent.py:153-166).
+ * legal_offset; 0 = never expanded).  Unspecified: top_index / top_visits / top_q at
+ * n_top and beyond, and out / visits_out of a game the kernel rejects (too many children,
+ * log table too short: the call returns BK_EINVAL).  Replaces the
+ * per-iteration Python loop of FastMCTSAgent.think (fast_mcts_agent.py:153-166).
  */
 #define BK_FASTMCTS_TOP 10
 #define BK_FASTMCTS_MAX_CHILDREN 2048

@@ -96,3 +96,17 @@ def test_random_children_match_reference_argmax(gpu):
         totals = rng.rand(k) * visits * 2.0
         kids = list(zip(visits.tolist(), totals.tolist()))
         assert gpu.fastmcts_select(visits, totals, n, LOGS, C) == ref_select(kids, n)
+
+
+@pytest.mark.parametrize("k", [1, 64, 65, 128, 129, 2048])
+def test_exact_ties_pick_the_first_child(gpu, k):
+    """k children of equal visits and totals have bit-equal UCB values: max() keeps the
+    first.  One strictly better child anywhere (first lane, last lane of the first pass,
+    first child of a lane's second pass, last child) wins wherever it sits."""
+    visits, n = [2] * k, 2 * k
+    assert gpu.fastmcts_select(visits, [1.25] * k, n, LOGS, C) == 0
+    for better in sorted({0, 63, 64, k - 1} & set(range(k))):
+        totals = [1.25] * k
+        totals[better] = 1.5
+        assert ref_select(list(zip(visits, totals)), n) == better
+        assert gpu.fastmcts_select(visits, totals, n, LOGS, C) == better, (k, better)
