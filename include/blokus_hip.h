@@ -673,6 +673,40 @@ int bk_snapshot_features(bk_handle h, const bk_state* states, const bk_fset* set
 /* sizeof(bk_snapshot_rec) as the library was compiled (binding checks; no GPU call). */
 int bk_snapshot_rec_size(void);
 
+/*
+ * bk_winprob_eval -- the learned evaluator of mcts/learned_evaluator.py for a pairwise logistic
+ * regression (model_type "pairwise_logreg"), n boards and all four players of each in one launch
+ * (added within ABI 7: new symbols only).  The block builds the board's four snapshot rows as
+ * bk_snapshot_features does (same states / sets / turn_index / max_turns, rows kept on the
+ * device), then scores player p against each opponent q, q ascending:
+ *     x_k = f[p][k] - f[q][k];  z_k = (x_k - mean[k]) / scale[k];  u_k = z_k * coef[k]
+ *     t = ((..((0 + u_0) + u_1)..) + u_33) + intercept;  s = 1 / (1 + exp(-t))
+ *     prob[4 i + p] = ((s_q0 + s_q1) + s_q2) / 3.0
+ * every step one correctly rounded double operation (no FMA) except exp (<= 1 ulp), so
+ * pair_logit[(4 i + p) * 3 + j] (t against the j-th opponent) equals the same chain in CPython
+ * floats bit for bit.  A very large |t| gives exactly 0.0 or 1.0, never NaN.
+ * status[i] is the board's bk_snapshot_rec.status (BK_SNAP_ST_* bits; prob is not to be
+ * trusted when it is non-zero).
+ */
+typedef struct bk_winprob_model {       /* POD; columns in BK_SNAPSHOT_COLUMNS order */
+    double mean[BK_SNAPSHOT_COLUMNS];   /* StandardScaler mean_  (0 where absent)   */
+    double scale[BK_SNAPSHOT_COLUMNS];  /* StandardScaler scale_ (1 where absent)   */
+    double coef[BK_SNAPSHOT_COLUMNS];   /* LogisticRegression coef_[0] (0 where the artifact has no such column) */
+    double intercept;
+} bk_winprob_model;
+/* sizeof(bk_winprob_model) as the library was compiled (binding checks; no GPU call). */
+int bk_winprob_model_size(void);
+/* turn_index may be NULL: each board's move_count, as the reference's evaluator passes.
+   prob (n x 4) and status (n) are required, pair_logit (n x 4 x 3) may be NULL.  model is
+   always a host pointer (it travels in the kernel arguments).  mem as bk_snapshot_features
+   (device pointers: sets 16-byte, states, prob and pair_logit 8-byte, turn_index 4-byte
+   aligned).  BK_EINVAL, before any GPU work, for null states, sets, model, prob or status,
+   n < 0, max_turns < 0, a non-finite value in the model or a scale of 0; n == 0 is BK_OK
+   without a launch; timed for bk_last_kernel_ms ("k_winprob"). */
+int bk_winprob_eval(bk_handle h, const bk_state* states, const bk_fset* sets, int32_t n,
+                    const int32_t* turn_index, int32_t max_turns, const bk_winprob_model* model,
+                    double* prob, double* pair_logit, uint8_t* status, int mem);
+
 /* Average duration (ms) of the most recent bk_rollout/bk_movegen kernel on the handle
    stream, measured with HIP events around that launch. */
 int bk_last_kernel_ms(bk_handle h, float* ms);

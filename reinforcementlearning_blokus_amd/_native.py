@@ -38,6 +38,7 @@ EXPORTS = (
     "bk_debug_mcts_failure", "bk_mcts_set_done", "bk_host_alloc", "bk_host_free",
     "bk_telemetry", "bk_telemetry_set_tables", "bk_debug_telemetry_mt",
     "bk_snapshot_features", "bk_snapshot_rec_size",
+    "bk_winprob_eval", "bk_winprob_model_size",
 )
 # bk_debug_mcts_failure record (include/blokus_hip.h BK_DIAG_*)
 DIAG_WORDS = 64
@@ -148,6 +149,15 @@ SNAPSHOT_REC_DTYPE = np.dtype({
     "itemsize": 80})
 assert C.sizeof(BkSnapshotRec) == 80
 assert all(getattr(BkSnapshotRec, n).offset == SNAPSHOT_REC_DTYPE.fields[n][1] for n in SNAPSHOT_REC_DTYPE.names)
+
+
+class BkWinprobModel(C.Structure):
+    """bk_winprob_model: a pairwise logistic regression over the 34 snapshot columns."""
+    _fields_ = [("mean", C.c_double * SNAPSHOT_COLUMNS), ("scale", C.c_double * SNAPSHOT_COLUMNS),
+                ("coef", C.c_double * SNAPSHOT_COLUMNS), ("intercept", C.c_double)]
+
+
+assert C.sizeof(BkWinprobModel) == 8 * (3 * SNAPSHOT_COLUMNS + 1)
 
 
 class BkMctsCfg(C.Structure):
@@ -261,6 +271,9 @@ def load():
             "bk_debug_telemetry_mt": (C.c_int, [vp, C.c_int32]),
             "bk_snapshot_features": (C.c_int, [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int]),
             "bk_snapshot_rec_size": (C.c_int, []),
+            "bk_winprob_eval": (C.c_int, [vp, vp, vp, C.c_int32, vp, C.c_int32, P(BkWinprobModel), vp, vp, vp,
+                                          C.c_int]),
+            "bk_winprob_model_size": (C.c_int, []),
         }
         for name, (res, args) in sigs.items():
             f = getattr(L, name)
@@ -615,6 +628,15 @@ class Handle:
                                               C.c_void_p(turn_ptr or 0), int(max_turns), C.c_void_p(rec_ptr or 0),
                                               C.c_void_p(feat_ptr or 0), mem)
         self.check(rc, "bk_snapshot_features")
+
+    def winprob_eval(self, states_ptr, sets_ptr, n, turn_ptr, max_turns, model: BkWinprobModel, prob_ptr, logit_ptr,
+                     status_ptr, mem):
+        with self._lock:
+            rc = self._L.bk_winprob_eval(self._h, C.c_void_p(states_ptr or 0), C.c_void_p(sets_ptr or 0), n,
+                                         C.c_void_p(turn_ptr or 0), int(max_turns), C.byref(model),
+                                         C.c_void_p(prob_ptr or 0), C.c_void_p(logit_ptr or 0),
+                                         C.c_void_p(status_ptr or 0), mem)
+        self.check(rc, "bk_winprob_eval")
 
     def advance(self, roots_ptr, n_roots, index_ptr, n, cfg: BkRolloutCfg, seeds_ptr, out_ptr, mem):
         with self._lock:

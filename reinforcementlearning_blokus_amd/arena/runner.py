@@ -108,8 +108,8 @@ class _GameplayFastMCTSAdapter:
 
 def build_agent(config: AgentConfig, seed: int):
     """Agent adapter from configuration (:415-492).  ``mcts`` seats search with the
-    reference's default HeuristicAgent rollouts (MCTSAgent "exact" backend); learned
-    evaluation options are out of scope and rejected by MCTSAgent."""
+    reference's default HeuristicAgent rollouts; the learned-evaluator options are forwarded
+    as the reference's runner forwards them (MCTSAgent then searches on its "exact" backend)."""
     kind = config.type.lower()
     params = dict(config.params)
     if kind == "random":
@@ -136,7 +136,11 @@ def build_agent(config: AgentConfig, seed: int):
             learned_model_path=params.get("learned_model_path"),
             leaf_evaluation_enabled=bool(params.get("leaf_evaluation_enabled", False)),
             progressive_bias_enabled=bool(params.get("progressive_bias_enabled", False)),
+            progressive_bias_weight=float(params.get("progressive_bias_weight", 0.25)),
             potential_shaping_enabled=bool(params.get("potential_shaping_enabled", False)),
+            potential_shaping_gamma=float(params.get("potential_shaping_gamma", 1.0)),
+            potential_shaping_weight=float(params.get("potential_shaping_weight", 1.0)),
+            potential_mode=str(params.get("potential_mode", "prob")),
             max_rollout_moves=int(params.get("max_rollout_moves", 50))))
     if kind == "fast_mcts":
         default_time = (float(config.thinking_time_ms) / 1000.0 if config.thinking_time_ms is not None

@@ -8,6 +8,7 @@
 //   engine/game.py:182-349            game over / GameResult scoring
 //   engine/telemetry.py:17-198        collect_all_player_metrics (bk_telemetry)
 //   analytics/winprob/features.py:106-192 snapshot feature rows (bk_snapshot_features)
+//   mcts/learned_evaluator.py:95-144  pairwise_logreg win probabilities (bk_winprob_eval)
 //
 // Design (DESIGN.md has the full story):
 //   * one lane = one board (one game); 64 games per wave, all control flow uniform
@@ -5936,6 +5937,14 @@ struct SnapArgs {
     double* feat;          // n x 4 x BK_SNAPSHOT_COLUMNS or null
 };
 
+struct WinprobArgs {
+    SnapArgs s;           // rec and feat unused; turn_index may be null (each board's move_count)
+    bk_winprob_model m;   // by value in the kernel arguments
+    double* prob;         // n x 4
+    double* pair_logit;   // n x 4 x 3 or null
+    uint8_t* status;      // n
+};
+
 static_assert(sizeof(bk_snapshot_rec) == 80 && sizeof(bk_snapshot_rec) % 8 == 0, "the record is copied out as dwords");
 static_assert(BK_SNAPSHOT_COLUMNS <= WAVE, "one lane per column");
 
@@ -5958,7 +5967,13 @@ constexpr SnapTab snap_tab() {
 }
 __constant__ SnapTab kSnapTab = snap_tab();
 
-__global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
+// The four rows of one board (the block's), left in s_feat.  EVAL = false is k_snapshot: the
+// records and rows also go to global memory and a call without a.feat stops after the records.
+// EVAL = true is k_winprob: nothing is written to global memory, every wave builds its row
+// (no barrier after it: the caller's), and a null a.turn_index means the board's move_count.
+// Returns the board's status word.
+template <bool EVAL>
+__device__ __forceinline__ uint32_t snap_rows(const SnapArgs& a, double (&s_feat)[SNAP_WAVES][BK_SNAPSHOT_COLUMNS]) {
 #pragma clang fp contract(off)
     __shared__ __attribute__((aligned(16))) uint2 s_rows[20 * WAVE];  // column p: player p's {B, C} rows
     __shared__ uint32_t s_own[4][20], s_occ[20], s_fr[4][20];
@@ -5966,7 +5981,6 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
     __shared__ uint32_t s_mob[4], s_fsz[4], s_dead, s_status;
     __shared__ int16_t s_otab[SNAP_WAVES][2 * WAVE];
     __shared__ double s_norm[SNAP_WAVES][BK_PIECES], s_wt[SNAP_WAVES][BK_PIECES];  // P_i / O_i, and that * S_i
-    __shared__ __attribute__((aligned(8))) double s_feat[SNAP_WAVES][BK_SNAPSHOT_COLUMNS];
     __shared__ __attribute__((aligned(8))) bk_snapshot_rec s_rec[SNAP_WAVES];
     constexpr int REC_WORDS = (int)(sizeof(bk_snapshot_rec) / 4);
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
@@ -5981,7 +5995,8 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
         (&s_own[0][0])[i] = plane_row(s->planes[i / 20], i % 20);
     }
     for (int i = tid; i < 4 * BK_PIECES; i += SNAP_WAVES * WAVE) (&s_pc[0][0])[i] = 0u;
-    for (int i = tid; i < SNAP_WAVES * REC_WORDS; i += SNAP_WAVES * WAVE) reinterpret_cast<bk_u32_alias*>(s_rec)[i] = 0u;
+    if (!EVAL)
+        for (int i = tid; i < SNAP_WAVES * REC_WORDS; i += SNAP_WAVES * WAVE) reinterpret_cast<bk_u32_alias*>(s_rec)[i] = 0u;
     if (tid == 0) s_status = 0u;
     __syncthreads();
     if (tid < 20) {
@@ -6081,16 +6096,16 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
     }
     const int corner_diff = (int)fsize - (int)opp_fr;
     const uint32_t used_count = (uint32_t)__builtin_popcount(used);
-    const int32_t turn = a.turn_index[board];
     const uint32_t ply = s->move_count;
+    const int32_t turn = EVAL && a.turn_index == nullptr ? (int32_t)ply : a.turn_index[board];
     if (lane < BK_PIECES) {
         const uint32_t P = s_pc[p][lane];
-        rec.piece_count[lane] = (uint16_t)P;
+        if (!EVAL) rec.piece_count[lane] = (uint16_t)P;
         const double nrm = __ddiv_rn((double)P, (double)kSnapTab.orients[lane]);  // count / n_orient
         s_norm[p][lane] = nrm;
         s_wt[p][lane] = __dmul_rn(nrm, (double)kSnapTab.size[lane]);              // normalized * size
     }
-    if (lane == 0) {
+    if (!EVAL && lane == 0) {
         rec.mobility = mob;
         rec.frontier_size = (uint16_t)fsize;
 #pragma unroll
@@ -6108,11 +6123,13 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
         rec.turn_index = turn;
     }
     tel_wave_sync();
-    if (a.rec != nullptr) {
-        bk_u32_alias* dst = reinterpret_cast<bk_u32_alias*>(a.rec + ((size_t)board * 4 + (size_t)p));
-        if (lane < REC_WORDS) dst[lane] = reinterpret_cast<const bk_u32_alias*>(&rec)[lane];
+    if (!EVAL) {
+        if (a.rec != nullptr) {
+            bk_u32_alias* dst = reinterpret_cast<bk_u32_alias*>(a.rec + ((size_t)board * 4 + (size_t)p));
+            if (lane < REC_WORDS) dst[lane] = reinterpret_cast<const bk_u32_alias*>(&rec)[lane];
+        }
+        if (a.feat == nullptr) return status;  // (uniform)
     }
-    if (a.feat == nullptr) return;  // (uniform)
     // compute_player_mobility_metrics' sums, pieces in ascending id, used pieces skipped: lane 0
     // total_norm, lanes 1..5 the size buckets, lane 6 total_weighted
     double acc = 0.0;
@@ -6164,11 +6181,59 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
         f[33] = __ddiv_rn((double)own_cells, cells);
     }
     tel_wave_sync();
-    if (lane < BK_SNAPSHOT_COLUMNS)
+    if (!EVAL && lane < BK_SNAPSHOT_COLUMNS)
         a.feat[((size_t)board * 4 + (size_t)p) * BK_SNAPSHOT_COLUMNS + (size_t)lane] = f[lane];
+    return status;
+}
+
+__global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
+    __shared__ __attribute__((aligned(8))) double s_feat[SNAP_WAVES][BK_SNAPSHOT_COLUMNS];
+    snap_rows<false>(a, s_feat);
+}
+
+// The learned evaluator (bk_winprob_eval; mcts/learned_evaluator.py:95-144 with a pairwise
+// logistic regression): the block builds the board's four rows as k_snapshot does, then wave
+// p scores player p against its three opponents q in ascending id.  Lane k < 34 forms
+// u_k = ((f[p][k] - f[q][k]) - mean[k]) / scale[k] * coef[k] for the three q and leaves them
+// in LDS; lane j < 3 adds opponent j's 34 terms in ascending k, then the intercept, and takes
+// s = 1 / (1 + exp(-t)); lane 0 averages the three.  One rounding per operation, no FMA.
+// exp overflows to +inf (s = 0) and underflows to 0 (s = 1) for very large |t|.
+__global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_winprob(WinprobArgs a) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(8))) double s_feat[SNAP_WAVES][BK_SNAPSHOT_COLUMNS];
+    __shared__ __attribute__((aligned(8))) double s_u[SNAP_WAVES][3][BK_SNAPSHOT_COLUMNS];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int p = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const size_t board = blockIdx.x;  // the grid is exactly n blocks
+    const uint32_t status = snap_rows<true>(a.s, s_feat);
+    __syncthreads();  // the four rows are complete
+    if (lane < BK_SNAPSHOT_COLUMNS) {
+        const double fp = s_feat[p][lane];
+        const double mean = a.m.mean[lane], scale = a.m.scale[lane], coef = a.m.coef[lane];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int q = j + (j >= p ? 1 : 0);
+            const double x = __dsub_rn(fp, s_feat[q][lane]);
+            s_u[p][j][lane] = __dmul_rn(__ddiv_rn(__dsub_rn(x, mean), scale), coef);
+        }
+    }
+    tel_wave_sync();
+    double sg = 0.0;
+    if (lane < 3) {
+        double t = 0.0;
+#pragma unroll 1
+        for (int k = 0; k < BK_SNAPSHOT_COLUMNS; ++k) t = __dadd_rn(t, s_u[p][lane][k]);
+        t = __dadd_rn(t, a.m.intercept);
+        sg = __ddiv_rn(1.0, __dadd_rn(1.0, exp(-t)));
+        if (a.pair_logit != nullptr) a.pair_logit[(board * 4 + (size_t)p) * 3 + (size_t)lane] = t;
+    }
+    const double s1 = __shfl(sg, 1), s2 = __shfl(sg, 2);
+    if (lane == 0) a.prob[board * 4 + (size_t)p] = __ddiv_rn(__dadd_rn(__dadd_rn(sg, s1), s2), 3.0);
+    if (tid == 0) a.status[board] = (uint8_t)status;
 }
 #else
 __global__ void k_snapshot(SnapArgs a);
+__global__ void k_winprob(WinprobArgs a);
 #endif
 
 #if BK_DEF(BK_U_HOST)
@@ -7074,6 +7139,65 @@ int bk_snapshot_features(bk_handle h, const bk_state* states, const bk_fset* set
     if (mem == BK_MEM_HOST) {
         if (rec) HIPCHK(h, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, h->cur));
         if (features) HIPCHK(h, hipMemcpyAsync(features, d_feat, feat_bytes, hipMemcpyDeviceToHost, h->cur));
+        HIPCHK(h, hipStreamSynchronize(h->cur));
+    }
+    return BK_OK;
+}
+
+int bk_winprob_model_size(void) { return (int)sizeof(bk_winprob_model); }
+
+int bk_winprob_eval(bk_handle h, const bk_state* states, const bk_fset* sets, int32_t n, const int32_t* turn_index,
+                    int32_t max_turns, const bk_winprob_model* model, double* prob, double* pair_logit, uint8_t* status,
+                    int mem) {
+    if (!h || !states || !sets || !model || !prob || !status || n < 0 || (mem != BK_MEM_HOST && mem != BK_MEM_DEVICE))
+        return set_err(h, BK_EINVAL, "bk_winprob_eval: invalid arguments%s", "");
+    if (max_turns < 0) return set_err(h, BK_EINVAL, "bk_winprob_eval: max_turns must be >= 0%s", "");
+    if (mem == BK_MEM_DEVICE && (((uintptr_t)sets & 15) || ((uintptr_t)states & 7) || ((uintptr_t)prob & 7) ||
+                                 ((uintptr_t)pair_logit & 7) || ((uintptr_t)turn_index & 3)))
+        return set_err(h, BK_EINVAL, "bk_winprob_eval: sets must be 16-byte, states, prob and pair_logit 8-byte, "
+                                     "turn_index 4-byte aligned%s", "");
+    if (!__builtin_isfinite(model->intercept))
+        return set_err(h, BK_EINVAL, "bk_winprob_eval: the model's intercept is not finite%s", "");
+    for (int k = 0; k < BK_SNAPSHOT_COLUMNS; ++k) {
+        if (!__builtin_isfinite(model->mean[k]) || !__builtin_isfinite(model->scale[k]) ||
+            !__builtin_isfinite(model->coef[k]))
+            return set_err(h, BK_EINVAL, "bk_winprob_eval: the model has a non-finite mean, scale or coef%s", "");
+        if (model->scale[k] == 0.0)
+            return set_err(h, BK_EINVAL, "bk_winprob_eval: the model has a scale of 0%s", "");
+    }
+    if (n == 0) return BK_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    BK_IDLE(h, "bk_winprob_eval");
+    void *d_states, *d_sets, *d_turn = nullptr;
+    int rc = stage_in(h, states, sizeof(bk_state) * (size_t)n, mem, &d_states, &h->d_in, &h->d_in_cap);
+    if (rc) return rc;
+    rc = stage_in(h, sets, sizeof(bk_fset) * (size_t)n, mem, &d_sets, &h->d_fin, &h->d_fin_cap);
+    if (rc) return rc;
+    if (turn_index) {
+        rc = stage_in(h, turn_index, sizeof(int32_t) * (size_t)n, mem, &d_turn, &h->d_aux, &h->d_aux_cap);
+        if (rc) return rc;
+    }
+    const size_t prob_bytes = sizeof(double) * 4 * (size_t)n, logit_bytes = sizeof(double) * 12 * (size_t)n;
+    double *d_prob = prob, *d_logit = pair_logit;
+    uint8_t* d_status = status;
+    if (mem == BK_MEM_HOST) {  // one staging buffer: prob, the pair logits, then the status bytes
+        rc = grow(h, &h->d_out, &h->d_out_cap, prob_bytes + logit_bytes + (size_t)n);
+        if (rc) return rc;
+        d_prob = (double*)h->d_out;
+        d_logit = pair_logit ? (double*)((char*)h->d_out + prob_bytes) : nullptr;
+        d_status = (uint8_t*)h->d_out + prob_bytes + logit_bytes;
+    }
+    WinprobArgs a{{(const bk_state*)d_states, (const bk_fset*)d_sets, (const int32_t*)d_turn, n, max_turns, nullptr, nullptr},
+                  *model, d_prob, d_logit, d_status};
+    HIPCHK(h, mark_start(h));
+    h->last_kernel = "k_winprob";
+    hipLaunchKernelGGL(k_winprob, dim3(n), dim3(SNAP_WAVES * WAVE), 0, h->cur, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, mark_end(h));
+    if (mem == BK_MEM_HOST) {
+        HIPCHK(h, hipMemcpyAsync(prob, d_prob, prob_bytes, hipMemcpyDeviceToHost, h->cur));
+        if (pair_logit) HIPCHK(h, hipMemcpyAsync(pair_logit, d_logit, logit_bytes, hipMemcpyDeviceToHost, h->cur));
+        HIPCHK(h, hipMemcpyAsync(status, d_status, (size_t)n, hipMemcpyDeviceToHost, h->cur));
         HIPCHK(h, hipStreamSynchronize(h->cur));
     }
     return BK_OK;

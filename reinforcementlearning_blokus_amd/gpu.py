@@ -223,6 +223,49 @@ class BlokusGPU:
                                       N.MEM_HOST)
         return rec, feat
 
+    def winprob_eval(self, states, sets, turn_index, max_turns: int, model, *, pair_logits: bool = False):
+        """The learned evaluator's win probabilities of n boards, four players each, in one
+        launch (bk_winprob_eval, k_winprob): states, sets and max_turns as snapshot_features,
+        turn_index int32[n] or None (each board's move_count, as the reference's evaluator),
+        model a N.BkWinprobModel or anything with ``as_native()`` (mcts.learned_evaluator.
+        WinProbModel).  Returns (prob float64 [n, 4], pair_logit float64 [n, 4, 3] or None,
+        status uint8 [n] of N.SNAP_ST_* bits: check it before trusting prob).  Torch cuda in
+        gives torch cuda out."""
+        native = model if isinstance(model, N.BkWinprobModel) else model.as_native()
+        if _is_torch(states):
+            import torch
+            n = states.shape[0]
+            _check_device_tensor(states, "states", torch.uint8, (n, 256), self.device)
+            _check_device_tensor(sets, "sets", torch.uint8, (n, N.FSET_DTYPE.itemsize), self.device)
+            if turn_index is not None:
+                _check_device_tensor(turn_index, "turn_index", torch.int32, (n,), self.device)
+            prob = torch.empty((n, 4), dtype=torch.float64, device=states.device)
+            logit = torch.empty((n, 4, 3), dtype=torch.float64, device=states.device) if pair_logits else None
+            status = torch.empty((n,), dtype=torch.uint8, device=states.device)
+            self._stream_from_torch()
+            self.handle.winprob_eval(states.data_ptr(), sets.data_ptr(), n,
+                                     turn_index.data_ptr() if turn_index is not None else 0, max_turns, native,
+                                     prob.data_ptr(), logit.data_ptr() if pair_logits else 0, status.data_ptr(),
+                                     N.MEM_DEVICE)
+            return prob, logit, status
+        st = np.ascontiguousarray(states).view(np.uint8)
+        fs = np.ascontiguousarray(sets).view(np.uint8)
+        n = st.size // 256
+        st, fs = st.reshape(n, 256), fs.reshape(n, N.FSET_DTYPE.itemsize)
+        ti = None
+        if turn_index is not None:
+            ti = np.ascontiguousarray(turn_index, dtype=np.int32).reshape(-1)
+            if ti.shape[0] != n:
+                raise ValueError(f"turn_index: {ti.shape[0]} entries for {n} boards")
+        prob = np.zeros((n, 4), dtype=np.float64)
+        logit = np.zeros((n, 4, 3), dtype=np.float64) if pair_logits else None
+        status = np.zeros(n, dtype=np.uint8)
+        self.handle.set_stream(None)
+        self.handle.winprob_eval(st.ctypes.data, fs.ctypes.data, n, ti.ctypes.data if ti is not None else 0, max_turns,
+                                 native, prob.ctypes.data, logit.ctypes.data if pair_logits else 0, status.ctypes.data,
+                                 N.MEM_HOST)
+        return prob, logit, status
+
     def has_moves(self, states):
         """uint8 mask per state: bit p set iff player p has a legal move (move_generator.py:961)."""
         if _is_torch(states):

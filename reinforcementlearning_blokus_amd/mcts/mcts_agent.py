@@ -24,7 +24,11 @@ have three GPU backends:
   HIP rollout kernel (bk_rollout, BK_SEM_ROLLOUT, Philox stream, naive move order) with
   UNIFORM random moves: statistically a random playout, not the reference's numbers,
   and not its heuristic policy.
-The learned-evaluator options of the reference are out of scope and rejected.
+The reference's learned-evaluator options (leaf evaluation, progressive bias, potential
+shaping; mcts/mcts_agent.py:376, :398-404, :426-468, :487-552) run on the ``exact`` backend:
+the host tree asks mcts.learned_evaluator for win probabilities, one bk_winprob_eval launch
+per call (parent and child of a progressive-bias update share a launch).  The in-kernel
+searches do not evaluate leaves, so ``search`` and ``kernel`` reject these options.
 """
 from __future__ import annotations
 
@@ -232,14 +236,27 @@ class MCTSAgent:
             raise ValueError("potential_mode must be either 'prob' or 'logit'.")
         if int(max_rollout_moves) <= 0:
             raise ValueError("max_rollout_moves must be > 0.")
-        if leaf_evaluation_enabled or progressive_bias_enabled or potential_shaping_enabled or learned_model_path:
-            raise ValueError("learned evaluation is not supported by the GPU MCTS (out of scope)")
+        self.leaf_evaluation_enabled = bool(leaf_evaluation_enabled)
+        self.progressive_bias_enabled = bool(progressive_bias_enabled)
+        self.potential_shaping_enabled = bool(potential_shaping_enabled)
+        self.potential_shaping_gamma = float(potential_shaping_gamma)
+        self.potential_shaping_weight = float(potential_shaping_weight)
+        self.potential_mode = potential_mode
+        self.learned_model_path = learned_model_path
+        self._requires_learned_evaluator = (self.leaf_evaluation_enabled or self.progressive_bias_enabled
+                                            or self.potential_shaping_enabled)
+        if self._requires_learned_evaluator and not self.learned_model_path:
+            raise ValueError("learned_model_path is required when learned evaluation, progressive bias, "
+                             "or potential shaping is enabled.")
+        learned = bool(self._requires_learned_evaluator or self.learned_model_path)
+        if learned and rollout_backend in ("search", "kernel"):
+            raise ValueError(f"rollout_backend='{rollout_backend}': the in-kernel search does not evaluate leaves; "
+                             "the learned-evaluator options need rollout_backend='exact'")
         self.iterations = iterations
         self.time_limit = time_limit
         self.exploration_constant = exploration_constant
         self.use_transposition_table = use_transposition_table
         self.max_rollout_moves = int(max_rollout_moves)
-        self.progressive_bias_enabled = False
         self.progressive_bias_weight = float(progressive_bias_weight)
         self.move_generator = get_shared_generator()
         self.piece_generator = PieceGenerator()
@@ -249,6 +266,8 @@ class MCTSAgent:
         if rollout_agent is None and rollout_backend != "kernel":
             rollout_agent = HeuristicAgent(seed=seed)  # the reference's default policy
         self.rollout_agent = rollout_agent
+        if rollout_backend is None and learned:
+            rollout_backend = "exact"
         if rollout_backend is None:
             rollout_backend = "search" if _search_policy(rollout_agent) is not None else "exact"
         self.rollout_backend = rollout_backend
@@ -265,6 +284,11 @@ class MCTSAgent:
         self._gpu = None
         self.transposition_table = TranspositionTable() if use_transposition_table else None
         self._gpu_tt = None  # "search" backend: the TT as a device-layout open-addressing table
+        self.learned_evaluator = None
+        if self.learned_model_path:
+            from .learned_evaluator import LearnedWinProbabilityEvaluator
+            self.learned_evaluator = LearnedWinProbabilityEvaluator(self.learned_model_path,
+                                                                    potential_mode=potential_mode, device=device)
         self.stats = self._fresh_stats()
 
     @staticmethod
@@ -438,16 +462,19 @@ class MCTSAgent:
     def _mcts_iteration(self, root: MCTSNode):
         node = self._selection(root)
         if not node.is_fully_expanded() and not node.is_terminal():
+            parent = node
             node = node.expand()
             if node is None:
                 return
+            self._update_progressive_bias(parent, node)
         self._backpropagation(node, self._simulation(node))
 
     def _selection(self, node: MCTSNode) -> MCTSNode:
         while not node.is_terminal():
             if not node.is_fully_expanded():
                 return node
-            node = node.select_child(self.exploration_constant, 0.0)
+            node = node.select_child(self.exploration_constant,
+                                     self.progressive_bias_weight if self.progressive_bias_enabled else 0.0)
         return node
 
     def _simulation(self, node: MCTSNode) -> float:
@@ -457,11 +484,40 @@ class MCTSAgent:
             if hit:
                 self.stats["transposition_hits"] += 1
                 return hit["reward"]
-        reward = self._rollout(node.board, node.player)
+        if self.leaf_evaluation_enabled and self.learned_evaluator is not None:
+            reward = self._evaluate_leaf(node.board, node.player)
+        else:
+            reward = self._rollout(node.board, node.player)
         if self.transposition_table:
             self.transposition_table.put(h, {"reward": reward})
         self.stats["rollout_rewards"].append(reward)
         return reward
+
+    def _evaluate_leaf(self, board: Board, player: Player) -> float:
+        """The learned win probability in place of a rollout (:439-451)."""
+        if self.learned_evaluator is None:
+            return self._rollout(board, player)
+        try:
+            probability = self.learned_evaluator.predict_player_win_probability(board, player)
+            self.stats["leaf_eval_calls"] += 1
+            return float(probability)
+        except Exception:  # noqa: BLE001 -- as the reference: count it and fall back to a rollout
+            self.stats["evaluator_errors"] += 1
+            return self._rollout(board, player)
+
+    def _update_progressive_bias(self, parent: MCTSNode, child: MCTSNode) -> None:
+        """child.prior_bias = V(child, parent's player) - V(parent, parent's player) (:453-468);
+        both boards go through one launch."""
+        if not self.progressive_bias_enabled or self.learned_evaluator is None:
+            return
+        try:
+            col = parent.player.value - 1
+            prob = self.learned_evaluator.predict_many([parent.board, child.board])
+            child.prior_bias = float(float(prob[1, col]) - float(prob[0, col]))
+            self.stats["progressive_bias_updates"] += 1
+        except Exception:  # noqa: BLE001
+            child.prior_bias = 0.0
+            self.stats["evaluator_errors"] += 1
 
     def _rollout(self, board: Board, player: Player) -> float:
         if self.rollout_backend == "kernel":
@@ -469,6 +525,13 @@ class MCTSAgent:
         sim = board.copy()
         cur = player
         start = sim.get_score(player)
+        initial_potential = None
+        if self.potential_shaping_enabled and self.learned_evaluator is not None:
+            try:
+                initial_potential = self.learned_evaluator.potential(sim, player)
+            except Exception:  # noqa: BLE001
+                self.stats["evaluator_errors"] += 1
+        moves_made = 0
         for _ in range(self.max_rollout_moves):
             legal = self.move_generator.get_legal_moves(sim, cur)
             if not legal:
@@ -477,10 +540,23 @@ class MCTSAgent:
             if mv is None or not sim.place_piece(_positions(mv), cur, mv.piece_id, validate=False):
                 break
             cur = _PLAYERS[(_PLAYERS.index(cur) + 1) % 4]
+            moves_made += 1
         reward = sim.get_score(player) - start
         if sim.is_game_over():  # never set inside a rollout (reference dead code kept for parity)
             w = sim.get_winner()
             reward += 100 if w == player else 10 if w is None else 0
+        # potential-based shaping, on truncated rollouts only (:535-552)
+        if (self.potential_shaping_enabled and self.learned_evaluator is not None and initial_potential is not None
+                and moves_made >= self.max_rollout_moves and not sim.is_game_over()):
+            try:
+                final_potential = self.learned_evaluator.potential(sim, player)
+                shaping_term = self.potential_shaping_weight * (
+                    (self.potential_shaping_gamma * final_potential) - initial_potential)
+                reward += shaping_term
+                if len(self.stats["potential_shaping_terms"]) < 2048:
+                    self.stats["potential_shaping_terms"].append(float(shaping_term))
+            except Exception:  # noqa: BLE001
+                self.stats["evaluator_errors"] += 1
         return reward
 
     def _rollout_kernel(self, board: Board, player: Player) -> float:
@@ -506,6 +582,14 @@ class MCTSAgent:
                                "exploration_constant": self.exploration_constant,
                                "use_transposition_table": self.use_transposition_table,
                                "max_rollout_moves": self.max_rollout_moves,
+                               "learned_model_path": self.learned_model_path,
+                               "leaf_evaluation_enabled": self.leaf_evaluation_enabled,
+                               "progressive_bias_enabled": self.progressive_bias_enabled,
+                               "progressive_bias_weight": self.progressive_bias_weight,
+                               "potential_shaping_enabled": self.potential_shaping_enabled,
+                               "potential_shaping_gamma": self.potential_shaping_gamma,
+                               "potential_shaping_weight": self.potential_shaping_weight,
+                               "potential_mode": self.potential_mode,
                                "rollout_backend": self.rollout_backend},
                 "stats": self.stats.copy()}
         if self.transposition_table:

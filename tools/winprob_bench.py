@@ -10,7 +10,10 @@ device tensors, records and feature matrix both written; each launch is timed by
 library's HIP events around k_snapshot (bk_last_kernel_ms).  One JSON line: boards/s from
 the median launch, and the spread (min / max / relative half-range).  --with-telemetry
 also times bk_telemetry (stability on, k = 3) on the same tensors in the same process,
-the launches of the two kernels alternating.
+the launches of the two kernels alternating.  --eval times bk_winprob_eval instead (the
+learned evaluator, k_winprob: device pointers, no pair logits; the model from --model),
+alternating with bk_snapshot_features writing the rows only, and reports both medians and
+their ratio.
 
 The comparison point is the reference's build_snapshot_runtime_context +
 extract_player_snapshot_features for the four players on one CPU core over the same ply
@@ -55,6 +58,42 @@ def cpu_reference(path: str, calls: int, lo: int, hi: int) -> dict:
             "median_s": statistics.median(times), "min_s": min(times), "max_s": max(times)}
 
 
+def eval_bench(gpu, args, d_st, d_fs, d_ti, n) -> dict:
+    """bk_winprob_eval (device pointers, no pair logits) and bk_snapshot_features writing the
+    rows only, alternating in this process on the same tensors; each launch timed by the
+    library's HIP events around it."""
+    import torch
+
+    from reinforcementlearning_blokus_amd.mcts.learned_evaluator import WinProbModel
+    with open(args.model) as fh:
+        doc = json.load(fh)
+    model = WinProbModel.from_dict(doc.get("model", doc))
+    ev_ms, sn_ms = [], []
+    for i in range(args.warmup + args.launches):
+        prob, _, status = gpu.winprob_eval(d_st, d_fs, d_ti, 2500, model)
+        gpu.synchronize()
+        assert gpu.last_kernel() == "k_winprob"
+        if i >= args.warmup:
+            ev_ms.append(gpu.last_kernel_ms())
+        _, feat = gpu.snapshot_features(d_st, d_fs, d_ti, 2500, records=False)
+        gpu.synchronize()
+        assert gpu.last_kernel() == "k_snapshot"
+        if i >= args.warmup:
+            sn_ms.append(gpu.last_kernel_ms())
+    torch.cuda.synchronize()
+    prob = prob.cpu().numpy()
+    emed, smed = statistics.median(ev_ms), statistics.median(sn_ms)
+    return {"tool": "winprob_bench", "mode": "eval", "boards": n, "min_ply": args.min_ply, "max_ply": args.max_ply,
+            "warmup": args.warmup, "launches": len(ev_ms),
+            "winprob_ms_median": emed, "winprob_ms_min": min(ev_ms), "winprob_ms_max": max(ev_ms),
+            "winprob_spread_rel": (max(ev_ms) - min(ev_ms)) / (2 * emed),
+            "snapshot_rows_ms_median": smed, "snapshot_rows_ms_min": min(sn_ms), "snapshot_rows_ms_max": max(sn_ms),
+            "snapshot_rows_spread_rel": (max(sn_ms) - min(sn_ms)) / (2 * smed),
+            "winprob_over_snapshot_rows": emed / smed, "boards_per_s": n / (emed * 1e-3),
+            "evaluations_per_s": 4 * n / (emed * 1e-3), "status_nonzero": int(status.cpu().numpy().astype(bool).sum()),
+            "prob_finite": bool(np.isfinite(prob).all()), "prob_mean": float(prob.mean())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--boards", type=int, default=4096)
@@ -64,6 +103,10 @@ def main():
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--seed", type=int, default=11)
     ap.add_argument("--with-telemetry", action="store_true", help="also time bk_telemetry on the same boards")
+    ap.add_argument("--eval", action="store_true",
+                    help="time bk_winprob_eval (no pair logits) alternating with bk_snapshot_features (rows only)")
+    ap.add_argument("--model", metavar="JSON", default=os.path.join(ROOT, "tests", "golden", "winprob_eval.json"),
+                    help="--eval: a WinProbModel JSON document, or a fixture holding one under \"model\"")
     ap.add_argument("--cpu-reference", metavar="PATH", help="time the reference checkout at PATH on the CPU instead")
     ap.add_argument("--cpu-calls", type=int, default=33)
     args = ap.parse_args()
@@ -93,6 +136,9 @@ def main():
     d_st = torch.from_numpy(states.view(np.uint8).reshape(n, 256).copy()).to(dev)
     d_fs = torch.from_numpy(sets.view(np.uint8).reshape(n, N.FSET_DTYPE.itemsize).copy()).to(dev)
     d_ti = torch.from_numpy(states["move_count"].astype(np.int32)).to(dev)
+    if args.eval:
+        print(json.dumps(eval_bench(gpu, args, d_st, d_fs, d_ti, n)), flush=True)
+        return
     ms, tel_ms = [], []
     for i in range(args.warmup + args.launches):
         rec, feat = gpu.snapshot_features(d_st, d_fs, d_ti, 2500)
