@@ -53,7 +53,12 @@ UNITS = {"host": 1, "movegen": 2, "rollout": 3, "rollout_fr": 4, "rollout_frh": 
 # VGPRs (+2 % frontier-order playouts/s) and k_mcts_coop_h needs 294 instead of 355
 # registers (profiles/r05/sweeps/r05b, r05a)
 _NO_MLICM = ("-mllvm", "-disable-machine-licm")
-UNIT_FLAGS = {"rollout_fr": _NO_MLICM, "coop": _NO_MLICM, "coop_h": _NO_MLICM}
+# Zero-column flags of the stencil classes (csrc/blokus_kernels.hip BK_CLASS_LIST): the
+# lane-pair scan of k_mcts_pair pays per class, so it takes the unsplit classes with
+# their shared flags; k_rollout_fr_h has no measurement and keeps the unflagged code
+# (profiles/r11)
+UNIT_FLAGS = {"rollout_fr": _NO_MLICM, "coop": _NO_MLICM, "coop_h": _NO_MLICM,
+              "mcts_pair": ("-DBK_STENCIL_COMMON",), "rollout_frh": ("-DBK_STENCIL_PLAIN",)}
 
 
 def compile_library(out: str, defines=(), verbose: bool = True, jobs: int = 0, unit_flags=None) -> str:

@@ -288,41 +288,84 @@ __device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
 #define LUT_ANDN 0x30    // a & ~b
 #define BITOP3(a, b, c, lut) __builtin_amdgcn_bitop3_b32((a), (b), (c), (lut))
 
-// One stencil class: height H, static term sequence T... (t = piece row * 4 + kind).
-// Term 0 sits at column 0 (no shift); term k >= 1 is shifted by the uniform column
-// sh[k].  For every anchor row r < 21 - H calls f(r, ok) with ok = legal anchor
-// columns (bit x = column x).
+// Zero-column flags of the class tokens (tools/gen_tables.py ZERO_MODES): a flagged term
+// sits at column 0 in every entry of its class and reads its plane row unshifted.  The
+// default list splits a class by its entries' zero patterns so that every column-0 term
+// is flagged.  Per unit (build.py UNIT_FLAGS), over the same table:
+// -DBK_STENCIL_COMMON scans the unsplit classes with the flags their entries share
+// (count_class_pair pays per class: an odd sub-class wastes half a scan);
+// -DBK_STENCIL_PLAIN scans them with no flag, which is the code from before the flags.
+#if defined(BK_STENCIL_PLAIN)
+#define BK_CLASS_LIST(X) BK_CLASS_LIST_PLAIN(X)
+#elif defined(BK_STENCIL_COMMON)
+#define BK_CLASS_LIST(X) BK_CLASS_LIST_COMMON(X)
+#else
+#define BK_CLASS_LIST(X) BK_CLASS_LIST_ZERO(X)
+#endif
+
+// One stencil class: height H, static term sequence T... (t = piece row * 8 + 4 * zero
+// + kind).  Term 0 sits at column 0 (no shift), and so does a term with the zero flag;
+// any other term k is shifted by the uniform column sh[k].  For every anchor row
+// r < 21 - H calls f(r, ok) with ok = legal anchor columns (bit x = column x).
 template <int H, int... T>
 struct StencilClass {
     static constexpr int NT = sizeof...(T);
     static constexpr int NR = 21 - H;
     static constexpr int ts[NT] = {T...};
+    static constexpr bool unshifted(int k) { return k == 0 || (ts[k] & 4) != 0; }
 
     template <int K>
     __device__ __forceinline__ static uint64_t tv(const Planes& P, int r, const uint32_t (&sh)[5]) {
-        constexpr int d = ts[K] >> 2, kind = ts[K] & 3;
+        constexpr int d = ts[K] >> 3, kind = ts[K] & 3;
         const uint64_t v = kind == 1 ? P.BCP[r + d] : kind == 2 ? P.BCV[r + d] : P.BC[r + d];
-        return K == 0 ? v : v >> sh[K];
+        return unshifted(K) ? v : v >> sh[K];
     }
     __device__ __forceinline__ static uint32_t lo(uint64_t v) { return (uint32_t)v; }
     __device__ __forceinline__ static uint32_t hi(uint64_t v) { return (uint32_t)(v >> 32); }
-    // OR of terms K.. into (b, c); the last C term folds into ok
-    template <int K>
+    // A row's first OR when every operand is an unshifted plane row: the value depends on
+    // nothing but the planes, so left to the optimizer it is hoisted out of the entry loop
+    // (past the no-lane-has-this-piece skip) and shared between classes, which keeps
+    // dozens of partial rows live across the stencil.  PIN issues the same instruction as
+    // a volatile asm, which stays where it is written; everything after it depends on it.
+    template <bool PIN>
+    __device__ __forceinline__ static uint32_t or3(uint32_t x, uint32_t y, uint32_t z) {
+        if constexpr (PIN) {
+            uint32_t r;
+            asm volatile("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xfe" : "=v"(r) : "v"(x), "v"(y), "v"(z));
+            return r;
+        } else {
+            return BITOP3(x, y, z, LUT_OR3);
+        }
+    }
+    template <bool PIN>
+    __device__ __forceinline__ static uint32_t or2(uint32_t x, uint32_t y) {
+        if constexpr (PIN) {
+            uint32_t r;
+            asm volatile("v_or_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+            return r;
+        } else {
+            return x | y;
+        }
+    }
+    // OR of terms K.. into (b, c); the last C term folds into ok.  INV: b and c are still
+    // plane rows as loaded (only at K = 1)
+    template <int K, bool INV = false>
     __device__ __forceinline__ static uint32_t fold(const Planes& P, int r, const uint32_t (&sh)[5], uint32_t b,
                                                     uint32_t c) {
         if constexpr (K + 2 <= NT - 1) {
+            constexpr bool pin = INV && unshifted(K) && unshifted(K + 1);
             const uint64_t t0 = tv<K>(P, r, sh), t1 = tv<K + 1>(P, r, sh);
-            b = BITOP3(b, lo(t0), lo(t1), LUT_OR3);
-            c = BITOP3(c, hi(t0), hi(t1), LUT_OR3);
+            b = or3<pin>(b, lo(t0), lo(t1));
+            c = or3<pin>(c, hi(t0), hi(t1));
             return fold<K + 2>(P, r, sh, b, c);
         } else if constexpr (K + 2 == NT) {  // two left: B merges both, C merges one + ok
             const uint64_t t0 = tv<K>(P, r, sh), t1 = tv<K + 1>(P, r, sh);
-            b = BITOP3(b, lo(t0), lo(t1), LUT_OR3);
-            c = c | hi(t0);
+            b = or3<INV && unshifted(K) && unshifted(K + 1)>(b, lo(t0), lo(t1));
+            c = or2<INV && unshifted(K)>(c, hi(t0));
             return BITOP3(c, hi(t1), b, LUT_OR2_ANDN);
         } else if constexpr (K + 1 == NT) {  // one left
             const uint64_t t0 = tv<K>(P, r, sh);
-            b = b | lo(t0);
+            b = or2<INV && unshifted(K)>(b, lo(t0));
             return BITOP3(c, hi(t0), b, LUT_OR2_ANDN);
         } else {
             return BITOP3(c, b, b, LUT_ANDN);
@@ -338,6 +381,7 @@ struct StencilClass {
         sh[0] = 0;
 #pragma unroll
         for (int k = 1; k < NT; ++k) {
+            if (unshifted(k)) continue;
             const uint32_t v = (w1 >> (3 * (k - 1))) & 7u;
             if constexpr (LANE_W1) sh[k] = v;
             else asm("v_mov_b32 %0, %1" : "=v"(sh[k]) : "s"(v));
@@ -347,7 +391,7 @@ struct StencilClass {
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             const uint64_t t0 = tv<0>(P, r, sh);
-            f(r, fold<1>(P, r, sh, lo(t0), hi(t0)));
+            f(r, fold<1, true>(P, r, sh, lo(t0), hi(t0)));
             __builtin_amdgcn_sched_barrier(0);
         }
     }

@@ -1,0 +1,191 @@
+"""The stencil with unshifted column-0 terms (csrc/orient_table.h zero flags,
+StencilClass::tv) computes what the shifted one did, in every kernel family built on it.
+
+Dense masks of all 91 orientations (bk_movegen_mask, staged and per-lane stores) for 32
+boards x 4 players against the oracle's naive lists: 28 random-bit boards on which every
+orientation has a legal anchor with its box at each board edge, and 4 strip boards whose
+free cells are three columns / rows wide along one edge, so a piece as wide (tall) as the
+strip fits only with its box at column 0, at column 20 - W, at row 0 or at row 20 - H.
+256 frontier-order and 256 naive-order arena playouts from 4 twenty-ply roots against the
+oracle's Philox replay (k_rollout_fr, k_rollout), and 64 searches x 64 iterations of
+k_mcts_pair (count_class_pair) against the oracle's search.  Tolerance: exact.
+"""
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as O
+from reinforcementlearning_blokus_amd import _native as N
+from tests import rules_reference as R
+from tests.helpers import mt_array, oracle_fset, oracle_states, pack_many
+
+pytestmark = pytest.mark.gpu
+
+SEED = 20260311
+STRIP = 3
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    from reinforcementlearning_blokus_amd.gpu import BlokusGPU
+    return BlokusGPU(0)
+
+
+def strip_states():
+    """[(edge, state)]: opponents own every cell but a STRIP-wide band along one edge; the
+    mover (player 0) owns one cell just outside the band, so the band holds two corner cells."""
+    out = []
+    for edge in ("left", "right", "top", "bottom"):
+        free = np.zeros((R.SIZE, R.SIZE), dtype=bool)
+        if edge == "left":
+            free[:, :STRIP] = True
+            own = (10, STRIP)
+        elif edge == "right":
+            free[:, R.SIZE - STRIP:] = True
+            own = (10, R.SIZE - STRIP - 1)
+        elif edge == "top":
+            free[:STRIP, :] = True
+            own = (STRIP, 10)
+        else:
+            free[R.SIZE - STRIP:, :] = True
+            own = (R.SIZE - STRIP - 1, 10)
+        g = np.zeros((4, R.SIZE, R.SIZE), dtype=bool)
+        for r, c in np.argwhere(~free):
+            g[1 + (r + c) % 3, r, c] = True
+        g[:, own[0], own[1]] = False
+        g[0, own[0], own[1]] = True
+        out.append((edge, R.make_state(g)))
+    return out
+
+
+@pytest.fixture(scope="module")
+def mask_case():
+    """(states[32], bool[128, 91, 20, 20] oracle sets, board-major, players 0..3)."""
+    strips = strip_states()
+    states = np.concatenate([R.random_bit_states()[:28]] + [s for _, s in strips])
+    assert len(states) == 32
+
+    def one(k):
+        m = np.zeros(N.N_ORIENTS * 400, dtype=bool)
+        m[O.legal_moves(R.oracle_board(states[k // 4]), k % 4, O.ORDER_NAIVE)] = True
+        return m.reshape(N.N_ORIENTS, 20, 20)
+
+    with ThreadPoolExecutor(16) as ex:
+        ref = np.stack(list(ex.map(one, range(4 * len(states)))))
+    return states, ref
+
+
+def test_boards_reach_the_edges(mask_case):
+    """Reference side: the random boards put every orientation's box at each of the four
+    edges; on each strip board the mover's orientations as wide (tall) as the strip have
+    legal anchors, all of them at the edge."""
+    states, ref = mask_case
+    per = ref.reshape(len(states), 4, N.N_ORIENTS, 20, 20)
+    hits = R.edge_pairs_hit(states[:28], per[:28])
+    assert (hits > 0).all(), np.argwhere(hits == 0).tolist()
+    for k, edge in enumerate(("left", "right", "top", "bottom")):
+        m = per[28 + k, 0]
+        seen = 0
+        for g in range(N.N_ORIENTS):
+            h, w = R.box(g)
+            if (w if edge in ("left", "right") else h) != STRIP or not m[g].any():
+                continue
+            seen += 1
+            rows, cols = np.nonzero(m[g])
+            want = {"left": cols == 0, "right": cols == R.SIZE - w, "top": rows == 0, "bottom": rows == R.SIZE - h}
+            assert want[edge].all(), (edge, g)
+        print(edge, "orientations that fit only at the edge:", seen)
+        assert seen >= 8, (edge, seen)
+
+
+def test_masks_match_oracle(gpu, mask_case):
+    states, ref = mask_case
+    n = len(states)
+    st = np.repeat(states, 4)
+    players = np.tile(np.arange(4, dtype=np.uint8), n)
+    refcnt = ref.reshape(4 * n, -1).sum(axis=1)
+    print("board-players", 4 * n, "oracle moves", int(refcnt.sum()))
+    try:
+        for stage, kernel in ((1, "k_movegen_ml4"), (0, "k_movegen_m")):
+            gpu.tune(MG_STAGE=stage)
+            cnt, masks = gpu.movegen_mask(st, players)
+            assert gpu.last_kernel() == kernel
+            bad = np.flatnonzero((R.masks_to_bool(masks) != ref).reshape(4 * n, -1).any(axis=1))
+            assert not len(bad), (kernel, [(int(k) // 4, int(k) % 4) for k in bad[:8]])
+            assert np.array_equal(cnt, refcnt), kernel
+    finally:
+        gpu.tune(MG_STAGE=None)
+
+
+@pytest.fixture(scope="module")
+def roots():
+    boards = oracle_states(4, seed0=9300, lo=20, hi=20)
+    st = pack_many(boards)
+    assert (st["move_count"] == 20).all()
+    return st, np.array([oracle_fset(b) for b in boards], dtype=N.FSET_DTYPE)
+
+
+@pytest.mark.parametrize("order", ["frontier", "naive"])
+def test_playouts_match_oracle(gpu, roots, order):
+    st, fs = roots
+    n = 256
+    idx = (np.arange(n) % len(st)).astype(np.int32)
+    if order == "frontier":
+        res = gpu.rollout_frontier(st, fs, n, semantics=N.SEM_ARENA, rng=N.RNG_PHILOX, seed=SEED, root_index=idx)
+        assert gpu.last_kernel() == "k_rollout_fr"
+    else:
+        res = gpu.rollout(st, n, semantics=N.SEM_ARENA, rng=N.RNG_PHILOX, seed=SEED, root_index=idx)
+        assert gpu.last_kernel() == "k_rollout"
+    gpu.synchronize()
+    assert res.shape == (n,) and (res["status"] == 0).all() and (res["plies"] > 0).all()
+
+    def one(pid):
+        i = int(idx[pid])
+        if order == "frontier":
+            b = O.board_from(st[i].tobytes(), fs[i])
+            r, _ = O.playout_arena_philox(b, SEED, pid, O.ORDER_FRONTIER)
+        else:
+            ost = O.State.from_buffer_copy(st[i].tobytes())
+            r, _ = O.playout_arena_philox(O.unpack(ost), SEED, pid, O.ORDER_NAIVE)
+        return bytes(r)
+
+    with ThreadPoolExecutor(16) as ex:
+        refs = list(ex.map(one, range(n)))
+    bad = [pid for pid in range(n) if res[pid].tobytes() != refs[pid]]
+    assert not bad, (order, len(bad), bad[:8])
+
+
+def test_mcts_pair_matches_oracle():
+    """64 searches x 64 iterations in one launch of k_mcts_pair (a batch this small goes to
+    the cooperative kernel unless told otherwise), game by game against or_mcts: best
+    move, rollout rewards, hit flags, TT size, RNG state."""
+    import ctypes as C
+
+    from reinforcementlearning_blokus_amd.gpu import BlokusGPU, MctsTT
+    gpu = BlokusGPU(0)
+    gpu.tune(MCTS_COOP=0)
+    n, iters, roll = 64, 64, 12
+    boards = oracle_states(n, seed0=9400, lo=8, hi=48)
+    players = [b.cur for b in boards]
+    ztab = O.zobrist_table(4)
+    roots = pack_many(boards)
+    roots["current_player"] = players
+    sets = np.array([oracle_fset(b) for b in boards], dtype=N.FSET_DTYPE)
+    hashes = np.array([O.lib().or_zobrist_hash(C.byref(b), ztab.ctypes.data_as(C.POINTER(C.c_uint64)))
+                       for b in boards], dtype=np.uint64)
+    mts = [O.numpy_mt(6000 + i) for i in range(n)]
+    mt = np.stack([mt_array(m) for m in mts])
+    tt = MctsTT(n)
+    r = gpu.mcts(roots, sets, np.asarray(players, np.uint8), hashes, iterations=iters, zobrist=ztab[None],
+                 mt_state=mt, tt=tt, max_rollout_moves=roll)
+    assert gpu.last_kernel() == "k_mcts_pair"
+    for g in range(n):
+        ott = O.TT()
+        ref = O.mcts(boards[g], players[g], iters, 1.414, roll, ztab, mts[g], ott)
+        assert int(r["out"][g]["status"]) == 0, g
+        assert int(r["out"][g]["best_move"]) == ref["move"], g
+        assert r["rewards"][g].tolist() == ref["rewards"].tolist(), g
+        assert r["hit_flags"][g].tolist() == ref["hit_flags"].tolist(), g
+        assert int(tt.count[g]) == ott.count, g
+        assert np.array_equal(mt[g], mt_array(mts[g])), g
