@@ -6284,6 +6284,8 @@ __global__ void k_winprob(WinprobArgs a);
 // ------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------
+struct Buf { void* p = nullptr; size_t cap = 0; };  // device memory that grow() owns
+
 struct bk_handle_s {
     int device = 0;
     hipStream_t own = nullptr, cur = nullptr;
@@ -6291,24 +6293,25 @@ struct bk_handle_s {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     char err[512] = {0};
-    // device staging / scratch
-    void* d_in = nullptr; size_t d_in_cap = 0;
-    void* d_out = nullptr; size_t d_out_cap = 0;
-    void* d_aux = nullptr; size_t d_aux_cap = 0;
-    void* d_aux2 = nullptr; size_t d_aux2_cap = 0;
-    void* d_slab = nullptr; size_t d_slab_cap = 0;
-    void* d_fin = nullptr; size_t d_fin_cap = 0;     // frontier: root tables
-    void* d_fout = nullptr; size_t d_fout_cap = 0;   // frontier: advanced tables
-    void* d_fslab = nullptr; size_t d_fslab_cap = 0; // frontier: per-slot records
-    void* d_mc = nullptr; size_t d_mc_cap = 0;       // bk_mcts: staged inputs/outputs
-    void* d_mclane = nullptr; size_t d_mclane_cap = 0; // bk_mcts: per-slot records
-    void* d_rh = nullptr; size_t d_rh_cap = 0;       // bk_mcts: root hashes computed on the device
-    void* d_step = nullptr; size_t d_step_cap = 0;   // bk_arena_step: staged extras
+    // The arena holds every staged copy of one BK_MEM_HOST call (Staging below).  Such a
+    // call ends in a synchronise, so the next one may regrow or overwrite it.  The work
+    // buffers stay apart: BK_MEM_DEVICE calls use them too, and under BK_MCTS_ASYNC they
+    // are still in flight when bk_mcts returns.
+    enum {
+        ARENA,
+        SLAB,     // playouts and bk_mcts: per-slot scratch words
+        FSLAB,    // frontier: per-slot records
+        MCLANE,   // bk_mcts: per-slot records
+        NODES,    // bk_mcts: the node pool when the caller passes none
+        RH,       // bk_mcts: root hashes computed on the device
+        STARTED,  // bk_mcts: searches started (mc_mark_started)
+        MTWORK,   // BK_MCTS_STATE_ROWS: the searches' MT copies
+        NBUF
+    };
+    Buf buf[NBUF];  // grown on demand (grow), freed by bk_destroy
     uint32_t* d_counter = nullptr;
     uint32_t* d_diag = nullptr;        // bk_mcts failure record (mc_diag), sticky until reported
-    void* d_started = nullptr; size_t d_started_cap = 0;  // bk_mcts: searches started (mc_mark_started)
     uint64_t* mcts_done = nullptr;  // bk_mcts_set_done: per-search result words
-    void* d_mtwork = nullptr; size_t d_mtwork_cap = 0;  // BK_MCTS_STATE_ROWS: the searches' MT copies
     uint32_t diag_host[BK_DIAG_WORDS] = {0};  // the last record bk_synchronize reported
     bool diag_seen = false;
     uint32_t mcts_launches = 0;
@@ -6406,14 +6409,98 @@ static int take_diag(bk_handle h) {
 // A handle's scratch grows in stream order on the handle's current stream
 // (hipFreeAsync / hipMallocAsync): hipFree would wait for the whole device, stalling
 // every other stream's launches (the arena's search streams regrow as job sizes vary).
-static int grow(bk_handle h, void** p, size_t* cap, size_t need) {
-    if (need <= *cap) return BK_OK;
-    if (*p) (void)hipFreeAsync(*p, h->cur);
-    *p = nullptr; *cap = 0;
+// Growing frees the old block: a pointer taken from b.p before a grow of b is stale.
+static int grow(bk_handle h, Buf& b, size_t need) {
+    if (need <= b.cap) return BK_OK;
+    if (b.p) (void)hipFreeAsync(b.p, h->cur);
+    b.p = nullptr; b.cap = 0;
     size_t n = need + need / 2 + 256;
-    HIPCHK(h, hipMallocAsync(p, n, h->cur));
-    *cap = n;
+    HIPCHK(h, hipMallocAsync(&b.p, n, h->cur));
+    b.cap = n;
     return BK_OK;
+}
+
+// The buffers of one launch that the caller passes in host or device memory (`mem`).
+// An entry point declares them (in / out / inout), commits once, launches with dev(), and
+// finishes.  BK_MEM_DEVICE: dev() is the caller's pointer, and commit and finish do nothing
+// (no allocation, copy or synchronise: the call may be captured into a graph).
+// BK_MEM_HOST: commit lays the present sections out in the handle's arena at 256-byte
+// offsets (the kernels need 16 bytes for sets, rng_state and movegen rows, 8 elsewhere),
+// grows the arena once, before any pointer into it exists, and copies the inputs in;
+// finish copies the outputs back and waits.  A section whose pointer is null or that
+// has no bytes is absent: nothing is staged, and its dev() is null.
+struct Staging {
+    enum { IN = 1, OUT = 2, INOUT = 3, MAX = 16 };
+    struct Sec { const void* host; size_t bytes; int dir; void* dev; };
+    template <class T> struct Ref {
+        const Sec* s;
+        T* dev() const { return (T*)s->dev; }
+    };
+    bk_handle h;
+    int mem, n = 0;
+    Sec sec[MAX + 1];  // [MAX]: where declarations past MAX land (commit then fails)
+
+    Staging(bk_handle h, int mem) : h(h), mem(mem) {}
+    Staging(const Staging&) = delete;
+
+    template <class T> Ref<T> add(T* host, size_t bytes, int dir) {
+        Sec& s = sec[n < MAX ? n : MAX];
+        ++n;
+        s = Sec{host, bytes, dir, mem == BK_MEM_DEVICE ? const_cast<void*>((const void*)host) : nullptr};
+        return Ref<T>{&s};
+    }
+    template <class T> Ref<const T> in(const T* host, size_t bytes) { return add(host, bytes, IN); }
+    template <class T> Ref<T> out(T* host, size_t bytes) { return add(host, bytes, OUT); }
+    template <class T> Ref<T> inout(T* host, size_t bytes) { return add(host, bytes, INOUT); }
+
+    static size_t aligned(size_t x) { return (x + 255) & ~(size_t)255; }
+    static bool present(const Sec& s) { return s.host && s.bytes; }
+
+    int commit() {
+        if (n > MAX) return set_err(h, BK_EINVAL, "staging: more than %s sections", "16");
+        if (mem == BK_MEM_DEVICE) return BK_OK;
+        size_t tot = 0;
+        for (int i = 0; i < n; ++i)
+            if (present(sec[i])) tot += aligned(sec[i].bytes);
+        Buf& arena = h->buf[bk_handle_s::ARENA];
+        if (int rc = grow(h, arena, tot)) return rc;
+        char* p = (char*)arena.p;
+        for (int i = 0; i < n; ++i) {
+            if (!present(sec[i])) continue;
+            sec[i].dev = p;
+            p += aligned(sec[i].bytes);
+            if (sec[i].dir & IN)
+                HIPCHK(h, hipMemcpyAsync(sec[i].dev, sec[i].host, sec[i].bytes, hipMemcpyHostToDevice, h->cur));
+        }
+        return BK_OK;
+    }
+    // the device-to-host copies alone: for a caller that adds a copy of its own before it waits
+    int copy_out() {
+        if (mem == BK_MEM_DEVICE) return BK_OK;
+        for (int i = 0; i < n; ++i)
+            if (present(sec[i]) && (sec[i].dir & OUT))
+                HIPCHK(h, hipMemcpyAsync(const_cast<void*>(sec[i].host), sec[i].dev, sec[i].bytes,
+                                         hipMemcpyDeviceToHost, h->cur));
+        return BK_OK;
+    }
+    int finish() {
+        if (mem == BK_MEM_DEVICE) return BK_OK;
+        if (int rc = copy_out()) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->cur));
+        return BK_OK;
+    }
+};
+
+// The end of a synchronous guarded launch (playouts, bk_fastmcts, bk_mcts): the staged
+// outputs and the handle's counter words come back in one wait; the launch's own sticky
+// bit is cleared, and a tripped guard (counter word 1) is reported as `code` with `msg`.
+static int finish_guarded(bk_handle h, Staging& st, uint32_t own, int code, const char* msg) {
+    uint32_t ctr[4];
+    if (int rc = st.copy_out()) return rc;
+    HIPCHK(h, hipMemcpyAsync(ctr, h->d_counter, sizeof ctr, hipMemcpyDeviceToHost, h->cur));
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    if (int rc = clear_own_sticky(h, ctr[2], own)) return rc;  // reported here
+    return ctr[1] ? set_err(h, code, msg, "") : BK_OK;
 }
 
 extern "C" {
@@ -6496,10 +6583,8 @@ int bk_destroy(bk_handle h) {
     (void)hipSetDevice(h->device);
     if (h->busy) (void)hipStreamSynchronize(h->busy_stream);
     if (h->own) (void)hipStreamSynchronize(h->own);
-    void* bufs[] = {h->d_in, h->d_out, h->d_aux, h->d_aux2, h->d_slab, h->d_fin, h->d_fout, h->d_fslab,
-                    h->d_mc, h->d_mclane, h->d_step, h->d_counter, h->d_rh, h->d_diag, h->d_started, h->d_mtwork,
-                    h->d_tel};
-    for (void* b : bufs) if (b) (void)hipFree(b);
+    for (Buf& b : h->buf) if (b.p) (void)hipFree(b.p);
+    for (void* p : {(void*)h->d_counter, (void*)h->d_diag, h->d_tel}) if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->own) (void)hipStreamDestroy(h->own);
@@ -6648,13 +6733,26 @@ static hipError_t mark_end(bk_handle h) {
     return e;
 }
 
-static int stage_in(bk_handle h, const void* src, size_t bytes, int mem, void** dev, void** buf, size_t* cap) {
-    if (mem == BK_MEM_DEVICE) { *dev = const_cast<void*>(src); return BK_OK; }
-    int rc = grow(h, buf, cap, bytes);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(*buf, src, bytes, hipMemcpyHostToDevice, h->cur));
-    *dev = *buf;
-    return BK_OK;
+// Every timed launch: the event pair around it, and bk_last_kernel's name taken from the
+// kernel's symbol, so the two cannot disagree.
+#define BK_LAUNCH(h, kernel, grid, block, ...)                                          \
+    do {                                                                                \
+        HIPCHK(h, mark_start(h));                                                       \
+        (h)->last_kernel = #kernel;                                                     \
+        hipLaunchKernelGGL(kernel, grid, block, 0, (h)->cur, __VA_ARGS__);              \
+        HIPCHK(h, hipGetLastError());                                                   \
+        HIPCHK(h, mark_end(h));                                                         \
+    } while (0)
+
+// orientation groups of the movegen kernels for n board-players: about 4 waves per CU, at
+// least 8 groups (measured best at 4,096 and 16,384 board-players,
+// profiles/r02/sweeps/movegen_groups.jsonl)
+static int movegen_groups(bk_handle h, int32_t n) {
+    const int waves = (n + WAVE - 1) / WAVE;
+    int groups = (4 * h->num_cu + waves - 1) / waves;
+    groups = groups < 8 ? 8 : (groups > MG_GROUPS_DEFAULT_MAX ? MG_GROUPS_DEFAULT_MAX : groups);
+    groups = (int)tune_or(h, BK_TUNE_MG_GROUPS, groups);
+    return groups < 1 ? 1 : groups > MG_GROUPS_MAX ? MG_GROUPS_MAX : groups;
 }
 
 int bk_movegen(bk_handle h, const bk_state* states, const uint8_t* players, int32_t n, uint32_t* out_rows,
@@ -6664,50 +6762,19 @@ int bk_movegen(bk_handle h, const bk_state* states, const uint8_t* players, int3
     if (n == 0) return BK_OK;
     HIPCHK(h, hipSetDevice(h->device));
     BK_IDLE(h, "bk_movegen");
-    void *d_states, *d_players;
-    int rc = stage_in(h, states, sizeof(bk_state) * (size_t)n, mem, &d_states, &h->d_in, &h->d_in_cap);
-    if (rc) return rc;
-    rc = stage_in(h, players, (size_t)n, mem, &d_players, &h->d_aux, &h->d_aux_cap);
-    if (rc) return rc;
-    uint32_t* d_rows = out_rows;
-    uint32_t* d_count = out_count;
-    const size_t rows_bytes = sizeof(uint32_t) * (size_t)n * BK_NUM_ORIENTS * 20;
-    if (mem == BK_MEM_HOST) {
-        rc = grow(h, &h->d_out, &h->d_out_cap, (out_rows ? rows_bytes : 0) + sizeof(uint32_t) * (size_t)n);
-        if (rc) return rc;
-        d_count = (uint32_t*)h->d_out;
-        d_rows = out_rows ? (uint32_t*)((char*)h->d_out + sizeof(uint32_t) * (size_t)n + 0) : nullptr;
-        // keep 16-byte alignment of the rows block
-        if (d_rows) d_rows = (uint32_t*)(((uintptr_t)d_rows + 15) & ~(uintptr_t)15);
-        if (d_rows) { rc = grow(h, &h->d_out, &h->d_out_cap, rows_bytes + sizeof(uint32_t) * (size_t)n + 16);
-                      if (rc) return rc;
-                      d_count = (uint32_t*)h->d_out;
-                      d_rows = (uint32_t*)(((uintptr_t)((char*)h->d_out + sizeof(uint32_t) * (size_t)n) + 15) & ~(uintptr_t)15); }
-    } else if (out_rows && ((uintptr_t)out_rows & 15)) {
+    if (mem == BK_MEM_DEVICE && out_rows && ((uintptr_t)out_rows & 15))
         return set_err(h, BK_EINVAL, "bk_movegen: out_rows must be 16-byte aligned%s", "");
-    }
-    // orientation groups: about 4 waves per CU, at least 8 groups (measured best at 4,096
-    // and 16,384 board-players, profiles/r02/sweeps/movegen_groups.jsonl)
-    const int waves = (n + WAVE - 1) / WAVE;
-    int groups = (4 * h->num_cu + waves - 1) / waves;
-    groups = groups < 8 ? 8 : (groups > MG_GROUPS_DEFAULT_MAX ? MG_GROUPS_DEFAULT_MAX : groups);
-    groups = (int)tune_or(h, BK_TUNE_MG_GROUPS, groups);
-    if (groups < 1) groups = 1;
-    if (groups > MG_GROUPS_MAX) groups = MG_GROUPS_MAX;
-    MovegenArgs a{(const bk_state*)d_states, (const uint8_t*)d_players, n, d_rows, d_count, nullptr, groups, nullptr};
-    if (d_count) HIPCHK(h, hipMemsetAsync(d_count, 0, sizeof(uint32_t) * (size_t)n, h->cur));  // atomics add in
-    const int grid = waves * groups;
-    HIPCHK(h, mark_start(h));
-    h->last_kernel = "k_movegen_g";
-    hipLaunchKernelGGL(k_movegen_g, dim3(grid), dim3(WAVE), 0, h->cur, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, mark_end(h));
-    if (mem == BK_MEM_HOST) {
-        if (out_count) HIPCHK(h, hipMemcpyAsync(out_count, d_count, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, h->cur));
-        if (out_rows) HIPCHK(h, hipMemcpyAsync(out_rows, d_rows, rows_bytes, hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipStreamSynchronize(h->cur));
-    }
-    return BK_OK;
+    Staging st(h, mem);
+    const auto s_states = st.in(states, sizeof(bk_state) * (size_t)n);
+    const auto s_players = st.in(players, (size_t)n);
+    const auto s_count = st.out(out_count, sizeof(uint32_t) * (size_t)n);
+    const auto s_rows = st.out(out_rows, sizeof(uint32_t) * (size_t)n * BK_NUM_ORIENTS * 20);
+    if (int rc = st.commit()) return rc;
+    const int groups = movegen_groups(h, n);
+    MovegenArgs a{s_states.dev(), s_players.dev(), n, s_rows.dev(), s_count.dev(), nullptr, groups, nullptr};
+    if (a.out_count) HIPCHK(h, hipMemsetAsync(a.out_count, 0, sizeof(uint32_t) * (size_t)n, h->cur));  // atomics add in
+    BK_LAUNCH(h, k_movegen_g,dim3((n + WAVE - 1) / WAVE * groups), dim3(WAVE), a);
+    return st.finish();
 }
 
 int bk_movegen_mask(bk_handle h, const bk_state* states, const uint8_t* players, int32_t n, uint64_t* out_mask,
@@ -6719,32 +6786,17 @@ int bk_movegen_mask(bk_handle h, const bk_state* states, const uint8_t* players,
         return set_err(h, BK_EINVAL, "bk_movegen_mask: out_mask must be 8-byte aligned%s", "");
     HIPCHK(h, hipSetDevice(h->device));
     BK_IDLE(h, "bk_movegen_mask");
-    void *d_states, *d_players;
-    int rc = stage_in(h, states, sizeof(bk_state) * (size_t)n, mem, &d_states, &h->d_in, &h->d_in_cap);
-    if (rc) return rc;
-    rc = stage_in(h, players, (size_t)n, mem, &d_players, &h->d_aux, &h->d_aux_cap);
-    if (rc) return rc;
-    uint64_t* d_mask = out_mask;
-    uint32_t* d_count = out_count;
-    const size_t mask_bytes = sizeof(uint64_t) * 7 * BK_NUM_ORIENTS * (size_t)n;
-    if (mem == BK_MEM_HOST) {
-        const size_t cb = (sizeof(uint32_t) * (size_t)n + 15) & ~(size_t)15;
-        rc = grow(h, &h->d_out, &h->d_out_cap, cb + (out_mask ? mask_bytes : 0));
-        if (rc) return rc;
-        d_count = (uint32_t*)h->d_out;
-        d_mask = out_mask ? (uint64_t*)((char*)h->d_out + cb) : nullptr;
-    }
+    Staging st(h, mem);
+    const auto s_states = st.in(states, sizeof(bk_state) * (size_t)n);
+    const auto s_players = st.in(players, (size_t)n);
+    const auto s_count = st.out(out_count, sizeof(uint32_t) * (size_t)n);
+    const auto s_mask = st.out(out_mask, sizeof(uint64_t) * 7 * BK_NUM_ORIENTS * (size_t)n);
+    if (int rc = st.commit()) return rc;
     // groups as bk_movegen; sets of 64 board-players rounded up to a multiple of the XCDs
-    const int waves = (n + WAVE - 1) / WAVE;
-    int groups = (4 * h->num_cu + waves - 1) / waves;
-    groups = groups < 8 ? 8 : (groups > MG_GROUPS_DEFAULT_MAX ? MG_GROUPS_DEFAULT_MAX : groups);
-    groups = (int)tune_or(h, BK_TUNE_MG_GROUPS, groups);
-    if (groups < 1) groups = 1;
-    if (groups > MG_GROUPS_MAX) groups = MG_GROUPS_MAX;
-    const int sets = ((waves + MG_XCDS - 1) / MG_XCDS) * MG_XCDS;
-    MovegenArgs a{(const bk_state*)d_states, (const uint8_t*)d_players, n, nullptr, d_count, nullptr, groups, d_mask};
-    if (d_count) HIPCHK(h, hipMemsetAsync(d_count, 0, sizeof(uint32_t) * (size_t)n, h->cur));  // atomics add in
-    HIPCHK(h, mark_start(h));
+    const int groups = movegen_groups(h, n);
+    const int sets = (((n + WAVE - 1) / WAVE + MG_XCDS - 1) / MG_XCDS) * MG_XCDS;
+    MovegenArgs a{s_states.dev(), s_players.dev(), n, nullptr, s_count.dev(), nullptr, groups, s_mask.dev()};
+    if (a.out_count) HIPCHK(h, hipMemsetAsync(a.out_count, 0, sizeof(uint32_t) * (size_t)n, h->cur));  // atomics add in
     // LDS-staged whole-line writes (k_movegen_ml): the groups' waves split over MG_PARTS
     // orientation ranges of one set each; BK_MG_STAGE=0 keeps the per-lane stores
     bool staged = out_mask != nullptr;
@@ -6763,31 +6815,14 @@ int bk_movegen_mask(bk_handle h, const bk_state* states, const uint8_t* players,
             while ((q + 1) * BK_NUM_ORIENTS / parts <= g) ++q;  // range q: [q 91 / parts, (q + 1) 91 / parts)
             a.part_masks[q][i >> 5] |= 1u << (i & 31);
         }
-        if (parts == 4) {
-            h->last_kernel = "k_movegen_ml4";
-            hipLaunchKernelGGL(k_movegen_ml4, grid, blk, 0, h->cur, a);
-        } else if (parts == 5) {
-            h->last_kernel = "k_movegen_ml5";
-            hipLaunchKernelGGL(k_movegen_ml5, grid, blk, 0, h->cur, a);
-        } else if (parts == 7) {
-            h->last_kernel = "k_movegen_ml7";
-            hipLaunchKernelGGL(k_movegen_ml7, grid, blk, 0, h->cur, a);
-        } else {
-            h->last_kernel = "k_movegen_ml13";
-            hipLaunchKernelGGL(k_movegen_ml13, grid, blk, 0, h->cur, a);
-        }
+        if (parts == 4) BK_LAUNCH(h, k_movegen_ml4, grid, blk, a);
+        else if (parts == 5) BK_LAUNCH(h, k_movegen_ml5, grid, blk, a);
+        else if (parts == 7) BK_LAUNCH(h, k_movegen_ml7, grid, blk, a);
+        else BK_LAUNCH(h, k_movegen_ml13, grid, blk, a);
     } else {
-        h->last_kernel = "k_movegen_m";
-        hipLaunchKernelGGL(k_movegen_m, dim3(sets * groups), dim3(WAVE), 0, h->cur, a);
+        BK_LAUNCH(h, k_movegen_m, dim3(sets * groups), dim3(WAVE), a);
     }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, mark_end(h));
-    if (mem == BK_MEM_HOST) {
-        if (out_count) HIPCHK(h, hipMemcpyAsync(out_count, d_count, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, h->cur));
-        if (out_mask) HIPCHK(h, hipMemcpyAsync(out_mask, d_mask, mask_bytes, hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipStreamSynchronize(h->cur));
-    }
-    return BK_OK;
+    return st.finish();
 }
 
 int bk_has_moves(bk_handle h, const bk_state* states, int32_t n, uint8_t* out_mask4, int mem) {
@@ -6796,26 +6831,13 @@ int bk_has_moves(bk_handle h, const bk_state* states, int32_t n, uint8_t* out_ma
     if (n == 0) return BK_OK;
     HIPCHK(h, hipSetDevice(h->device));
     BK_IDLE(h, "bk_has_moves");
-    void* d_states;
-    int rc = stage_in(h, states, sizeof(bk_state) * (size_t)n, mem, &d_states, &h->d_in, &h->d_in_cap);
-    if (rc) return rc;
-    uint8_t* d_mask = out_mask4;
-    if (mem == BK_MEM_HOST) {
-        rc = grow(h, &h->d_out, &h->d_out_cap, (size_t)n);
-        if (rc) return rc;
-        d_mask = (uint8_t*)h->d_out;
-    }
-    MovegenArgs a{(const bk_state*)d_states, nullptr, n, nullptr, nullptr, d_mask, 0, nullptr};
-    HIPCHK(h, mark_start(h));
-    h->last_kernel = "k_has_moves";
-    hipLaunchKernelGGL(k_has_moves, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, h->cur, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, mark_end(h));
-    if (mem == BK_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(out_mask4, d_mask, (size_t)n, hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipStreamSynchronize(h->cur));
-    }
-    return BK_OK;
+    Staging st(h, mem);
+    const auto s_states = st.in(states, sizeof(bk_state) * (size_t)n);
+    const auto s_mask = st.out(out_mask4, (size_t)n);
+    if (int rc = st.commit()) return rc;
+    MovegenArgs a{s_states.dev(), nullptr, n, nullptr, nullptr, s_mask.dev(), 0, nullptr};
+    BK_LAUNCH(h, k_has_moves, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), a);
+    return st.finish();
 }
 
 static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, const int32_t* root_index,
@@ -6848,74 +6870,29 @@ static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, 
     if (n_playouts == 0) return BK_OK;
     HIPCHK(h, hipSetDevice(h->device));
     BK_IDLE(h, "bk_rollout");
-    void *d_roots, *d_idx = nullptr, *d_seeds = nullptr;
-    int rc = stage_in(h, roots, sizeof(bk_state) * (size_t)n_roots, mem, &d_roots, &h->d_in, &h->d_in_cap);
+    if (root_index && mem == BK_MEM_HOST)
+        for (int32_t i = 0; i < n_playouts; ++i)
+            if (root_index[i] < 0 || root_index[i] >= n_roots)
+                return set_err(h, BK_EINVAL, "bk_rollout: root_index entry outside [0, n_roots)%s", "");
+    const size_t np = (size_t)n_playouts;
+    Staging st(h, mem);
+    const auto s_roots = st.in(roots, sizeof(bk_state) * (size_t)n_roots);
+    const auto s_idx = st.in(root_index, sizeof(int32_t) * np);
+    // compat_seeds only with the compat rng (bk_arena_advance / bk_arena_step carry cursors, rng_io, instead)
+    const auto s_seeds = st.in(cfg->rng == BK_RNG_NUMPY_MT ? compat_seeds : nullptr, sizeof(uint32_t) * 4 * np);
+    const auto s_rsets = st.in(root_sets, sizeof(bk_fset) * (size_t)n_roots);
+    const auto s_masks = st.in(seat_masks, np);
+    const auto s_rng = st.inout(rng_io, sizeof(uint32_t) * 16 * np);
+    const auto s_quick = st.in(quick_masks, np);
+    const auto s_forced = st.in(forced, sizeof(int32_t) * np);
+    const auto s_stop = st.out(stop_out, sizeof(bk_stop_info) * np);
+    // in host memory the outputs are copies of their own, also where the caller advances
+    // states and sets in place (bk_arena_advance / bk_arena_step)
+    const auto s_out = st.out(out, sizeof(bk_result) * np);
+    const auto s_ostates = st.out(out_states, sizeof(bk_state) * np);
+    const auto s_osets = st.out(out_sets, sizeof(bk_fset) * np);
+    int rc = st.commit();
     if (rc) return rc;
-    if (root_index) {
-        if (mem == BK_MEM_HOST)
-            for (int32_t i = 0; i < n_playouts; ++i)
-                if (root_index[i] < 0 || root_index[i] >= n_roots)
-                    return set_err(h, BK_EINVAL, "bk_rollout: root_index entry outside [0, n_roots)%s", "");
-        rc = stage_in(h, root_index, sizeof(int32_t) * (size_t)n_playouts, mem, &d_idx, &h->d_aux, &h->d_aux_cap);
-        if (rc) return rc;
-    }
-    if (cfg->rng == BK_RNG_NUMPY_MT && compat_seeds) {  // (bk_arena_advance carries cursors instead)
-        rc = stage_in(h, compat_seeds, sizeof(uint32_t) * 4 * (size_t)n_playouts, mem, &d_seeds, &h->d_aux2,
-                      &h->d_aux2_cap);
-        if (rc) return rc;
-    }
-    void* d_rsets = nullptr;
-    if (fr) {
-        rc = stage_in(h, root_sets, sizeof(bk_fset) * (size_t)n_roots, mem, &d_rsets, &h->d_fin, &h->d_fin_cap);
-        if (rc) return rc;
-    }
-    void *d_masks = nullptr, *d_rng = nullptr, *d_quick = nullptr, *d_forced = nullptr;
-    bk_stop_info* d_stop = stop_out;
-    if (seat_masks) {  // bk_arena_advance / bk_arena_step
-        rc = stage_in(h, seat_masks, (size_t)n_playouts, mem, &d_masks, &h->d_aux, &h->d_aux_cap);
-        if (rc) return rc;
-        rc = stage_in(h, rng_io, sizeof(uint32_t) * 16 * (size_t)n_playouts, mem, &d_rng, &h->d_aux2, &h->d_aux2_cap);
-        if (rc) return rc;
-        // bk_arena_step's extras share one staging buffer (host mode): quick masks,
-        // forced moves, stop infos at 16-byte aligned offsets
-        const size_t qb = quick_masks ? ((size_t)n_playouts + 15) & ~(size_t)15 : 0;
-        const size_t fb = forced ? (sizeof(int32_t) * (size_t)n_playouts + 15) & ~(size_t)15 : 0;
-        const size_t sb = stop_out ? sizeof(bk_stop_info) * (size_t)n_playouts : 0;
-        if (mem == BK_MEM_HOST && (qb + fb + sb)) {
-            rc = grow(h, &h->d_step, &h->d_step_cap, qb + fb + sb);
-            if (rc) return rc;
-            char* base = (char*)h->d_step;
-            if (quick_masks) {
-                d_quick = base;
-                HIPCHK(h, hipMemcpyAsync(d_quick, quick_masks, (size_t)n_playouts, hipMemcpyHostToDevice, h->cur));
-            }
-            if (forced) {
-                d_forced = base + qb;
-                HIPCHK(h, hipMemcpyAsync(d_forced, forced, sizeof(int32_t) * (size_t)n_playouts,
-                                         hipMemcpyHostToDevice, h->cur));
-            }
-            if (stop_out) d_stop = (bk_stop_info*)(base + qb + fb);
-        } else {
-            d_quick = const_cast<uint8_t*>(quick_masks);
-            d_forced = const_cast<int32_t*>(forced);
-        }
-    }
-    bk_result* d_out = out;
-    bk_state* d_states = out_states;
-    bk_fset* d_osets = out_sets;
-    if (mem == BK_MEM_HOST) {
-        const size_t rb = out ? sizeof(bk_result) * (size_t)n_playouts : 0;
-        const size_t sb = out_states ? sizeof(bk_state) * (size_t)n_playouts : 0;
-        rc = grow(h, &h->d_out, &h->d_out_cap, rb + sb);
-        if (rc) return rc;
-        d_out = out ? (bk_result*)h->d_out : nullptr;
-        d_states = out_states ? (bk_state*)((char*)h->d_out + rb) : nullptr;
-        if (out_sets) {
-            rc = grow(h, &h->d_fout, &h->d_fout_cap, sizeof(bk_fset) * (size_t)n_playouts);
-            if (rc) return rc;
-            d_osets = (bk_fset*)h->d_fout;
-        }
-    }
     // persistent grid: every resident slot pulls playouts from the counter
     const bool heur = fr && ((cfg->heuristic_seats & 0xF) != 0 || seat_masks != nullptr);
     const int blk = heur ? HBLOCK : BLOCK;
@@ -6924,10 +6901,11 @@ static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, 
     if (blocks > need) blocks = need;
     if (blocks < 1) blocks = 1;
     const uint32_t nslots = (uint32_t)blocks * blk;
-    rc = grow(h, &h->d_slab, &h->d_slab_cap, sizeof(uint32_t) * SLAB_WORDS * (size_t)nslots);
+    Buf &slab = h->buf[bk_handle_s::SLAB], &fslab = h->buf[bk_handle_s::FSLAB];
+    rc = grow(h, slab, sizeof(uint32_t) * SLAB_WORDS * (size_t)nslots);
     if (rc) return rc;
     if (fr) {
-        rc = grow(h, &h->d_fslab, &h->d_fslab_cap, sizeof(FsLane) * (size_t)nslots);
+        rc = grow(h, fslab, sizeof(FsLane) * (size_t)nslots);
         if (rc) return rc;
     }
     HIPCHK(h, hipMemsetAsync(h->d_counter, 0, 2 * sizeof(uint32_t), h->cur));  // [2] is sticky
@@ -6935,14 +6913,14 @@ static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, 
     const uint64_t per_game = (cfg->semantics == BK_SEM_ROLLOUT ? (uint64_t)cfg->max_plies + 2u : 100u);
     uint64_t iters = 2 * per_lane * per_game + 64u;  // 2x: uneven hand-outs (handout 2)
     iters = (uint64_t)tune_or(h, BK_TUNE_DEBUG_MAX_ITERS, (int64_t)iters);  // tests: force the guard
-    RolloutArgs a{(const bk_state*)d_roots, n_roots, (const int32_t*)d_idx, n_playouts, *cfg,
-                  (const uint32_t*)d_seeds, d_out, (uint32_t*)h->d_slab, nslots, h->d_counter,
-                  (uint32_t)(iters > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : iters), d_states,
-                  (const bk_fset*)d_rsets, d_osets, fr ? (FsLane*)h->d_fslab : nullptr,
-                  (const uint8_t*)d_masks, (uint32_t*)d_rng, fr ? 0 : 2, 0u};
-    a.quick_masks = (const uint8_t*)d_quick;
-    a.forced = (const int32_t*)d_forced;
-    a.stop_out = d_stop;
+    RolloutArgs a{s_roots.dev(), n_roots, s_idx.dev(), n_playouts, *cfg, s_seeds.dev(), s_out.dev(),
+                  (uint32_t*)slab.p, nslots, h->d_counter,
+                  (uint32_t)(iters > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : iters), s_ostates.dev(),
+                  s_rsets.dev(), s_osets.dev(), fr ? (FsLane*)fslab.p : nullptr,
+                  s_masks.dev(), s_rng.dev(), fr ? 0 : 2, 0u};
+    a.quick_masks = s_quick.dev();
+    a.forced = s_forced.dev();
+    a.stop_out = s_stop.dev();
     // Playout hand-out.  Config 3 has 1.33 playouts per resident slot: pulled per lane
     // from one counter (handout 0), the extra third lands on lanes of EVERY wave, and each
     // wave then runs a second playout length with a third of its lanes; given to whole
@@ -6959,44 +6937,12 @@ static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, 
         int64_t ls = rest <= 0 ? 0 : rest >= (int64_t)nslots ? (int64_t)nslots : ((rest + WAVE - 1) / WAVE) * WAVE;
         a.long_slots = (uint32_t)ls;
     }
-    HIPCHK(h, mark_start(h));
-    if (heur) {
-        h->last_kernel = "k_rollout_fr_h";
-        hipLaunchKernelGGL(k_rollout_fr_h, dim3(blocks), dim3(HBLOCK), 0, h->cur, a);
-    } else if (fr) {
-        h->last_kernel = "k_rollout_fr";
-        hipLaunchKernelGGL(k_rollout_fr, dim3(blocks), dim3(BLOCK), 0, h->cur, a);
-    } else if (cfg->semantics == BK_SEM_ADVANCE) {
-        h->last_kernel = "k_advance";
-        hipLaunchKernelGGL(k_advance, dim3(blocks), dim3(BLOCK), 0, h->cur, a);
-    } else {
-        h->last_kernel = "k_rollout";
-        hipLaunchKernelGGL(k_rollout, dim3(blocks), dim3(BLOCK), 0, h->cur, a);
-    }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, mark_end(h));
-    if (mem == BK_MEM_HOST) {
-        if (out)
-            HIPCHK(h, hipMemcpyAsync(out, d_out, sizeof(bk_result) * (size_t)n_playouts, hipMemcpyDeviceToHost, h->cur));
-        if (out_states)
-            HIPCHK(h, hipMemcpyAsync(out_states, d_states, sizeof(bk_state) * (size_t)n_playouts,
-                                     hipMemcpyDeviceToHost, h->cur));
-        if (out_sets)
-            HIPCHK(h, hipMemcpyAsync(out_sets, d_osets, sizeof(bk_fset) * (size_t)n_playouts,
-                                     hipMemcpyDeviceToHost, h->cur));
-        if (rng_io)
-            HIPCHK(h, hipMemcpyAsync(rng_io, d_rng, sizeof(uint32_t) * 16 * (size_t)n_playouts,
-                                     hipMemcpyDeviceToHost, h->cur));
-        if (stop_out)
-            HIPCHK(h, hipMemcpyAsync(stop_out, d_stop, sizeof(bk_stop_info) * (size_t)n_playouts,
-                                     hipMemcpyDeviceToHost, h->cur));
-        uint32_t ctr[4];
-        HIPCHK(h, hipMemcpyAsync(ctr, h->d_counter, sizeof ctr, hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipStreamSynchronize(h->cur));
-        if (int rc = clear_own_sticky(h, ctr[2], BK_STICKY_GUARD)) return rc;  // reported here
-        if (ctr[1]) return set_err(h, BK_EOVERFLOW, "bk_rollout: iteration guard tripped%s", "");
-    }
-    return BK_OK;
+    if (heur) BK_LAUNCH(h, k_rollout_fr_h, dim3(blocks), dim3(HBLOCK), a);
+    else if (fr) BK_LAUNCH(h, k_rollout_fr, dim3(blocks), dim3(BLOCK), a);
+    else if (cfg->semantics == BK_SEM_ADVANCE) BK_LAUNCH(h, k_advance, dim3(blocks), dim3(BLOCK), a);
+    else BK_LAUNCH(h, k_rollout, dim3(blocks), dim3(BLOCK), a);
+    if (mem == BK_MEM_DEVICE) return BK_OK;  // a tripped guard stays sticky for bk_synchronize
+    return finish_guarded(h, st, BK_STICKY_GUARD, BK_EOVERFLOW, "bk_rollout: iteration guard tripped%s");
 }
 
 int bk_rollout(bk_handle h, const bk_state* roots, int32_t n_roots, const int32_t* root_index, int32_t n_playouts,
@@ -7115,31 +7061,15 @@ int bk_telemetry(bk_handle h, const bk_state* states, const bk_fset* sets, int32
         HIPCHK(h, hipStreamSynchronize(h->cur));  // the staging vector leaves scope
         h->tel_dirty = false;
     }
-    void *d_states, *d_sets;
-    int rc = stage_in(h, states, sizeof(bk_state) * (size_t)n, mem, &d_states, &h->d_in, &h->d_in_cap);
-    if (rc) return rc;
-    rc = stage_in(h, sets, sizeof(bk_fset) * (size_t)n, mem, &d_sets, &h->d_fin, &h->d_fin_cap);
-    if (rc) return rc;
-    const size_t out_bytes = sizeof(bk_player_metrics) * 4 * (size_t)n;
-    bk_player_metrics* d_outp = out;
-    if (mem == BK_MEM_HOST) {
-        rc = grow(h, &h->d_out, &h->d_out_cap, out_bytes);
-        if (rc) return rc;
-        d_outp = (bk_player_metrics*)h->d_out;
-    }
-    TelArgs a{(const bk_state*)d_states, (const bk_fset*)d_sets, n, cfg->k_samples,
-              (cfg->flags & BK_TEL_STABILITY) ? 1 : 0, (const uint32_t*)((char*)h->d_tel + tab_bytes),
-              (const double*)h->d_tel, d_outp};
-    HIPCHK(h, mark_start(h));
-    h->last_kernel = "k_telemetry";
-    hipLaunchKernelGGL(k_telemetry, dim3(n), dim3(TEL_WAVES * WAVE), 0, h->cur, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, mark_end(h));
-    if (mem == BK_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(out, d_outp, out_bytes, hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipStreamSynchronize(h->cur));
-    }
-    return BK_OK;
+    Staging st(h, mem);
+    const auto s_states = st.in(states, sizeof(bk_state) * (size_t)n);
+    const auto s_sets = st.in(sets, sizeof(bk_fset) * (size_t)n);
+    const auto s_out = st.out(out, sizeof(bk_player_metrics) * 4 * (size_t)n);
+    if (int rc = st.commit()) return rc;
+    TelArgs a{s_states.dev(), s_sets.dev(), n, cfg->k_samples, (cfg->flags & BK_TEL_STABILITY) ? 1 : 0,
+              (const uint32_t*)((char*)h->d_tel + tab_bytes), (const double*)h->d_tel, s_out.dev()};
+    BK_LAUNCH(h, k_telemetry, dim3(n), dim3(TEL_WAVES * WAVE), a);
+    return st.finish();
 }
 
 int bk_snapshot_rec_size(void) { return (int)sizeof(bk_snapshot_rec); }
@@ -7157,35 +7087,16 @@ int bk_snapshot_features(bk_handle h, const bk_state* states, const bk_fset* set
     if (n == 0) return BK_OK;
     HIPCHK(h, hipSetDevice(h->device));
     BK_IDLE(h, "bk_snapshot_features");
-    void *d_states, *d_sets, *d_turn;
-    int rc = stage_in(h, states, sizeof(bk_state) * (size_t)n, mem, &d_states, &h->d_in, &h->d_in_cap);
-    if (rc) return rc;
-    rc = stage_in(h, sets, sizeof(bk_fset) * (size_t)n, mem, &d_sets, &h->d_fin, &h->d_fin_cap);
-    if (rc) return rc;
-    rc = stage_in(h, turn_index, sizeof(int32_t) * (size_t)n, mem, &d_turn, &h->d_aux, &h->d_aux_cap);
-    if (rc) return rc;
-    const size_t rec_bytes = sizeof(bk_snapshot_rec) * 4 * (size_t)n;
-    const size_t feat_bytes = sizeof(double) * BK_SNAPSHOT_COLUMNS * 4 * (size_t)n;
-    bk_snapshot_rec* d_rec = rec;
-    double* d_feat = features;
-    if (mem == BK_MEM_HOST) {  // one staging buffer: the records, then the rows (rec_bytes is a multiple of 8)
-        rc = grow(h, &h->d_out, &h->d_out_cap, rec_bytes + feat_bytes);
-        if (rc) return rc;
-        d_rec = rec ? (bk_snapshot_rec*)h->d_out : nullptr;
-        d_feat = features ? (double*)((char*)h->d_out + rec_bytes) : nullptr;
-    }
-    SnapArgs a{(const bk_state*)d_states, (const bk_fset*)d_sets, (const int32_t*)d_turn, n, max_turns, d_rec, d_feat};
-    HIPCHK(h, mark_start(h));
-    h->last_kernel = "k_snapshot";
-    hipLaunchKernelGGL(k_snapshot, dim3(n), dim3(SNAP_WAVES * WAVE), 0, h->cur, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, mark_end(h));
-    if (mem == BK_MEM_HOST) {
-        if (rec) HIPCHK(h, hipMemcpyAsync(rec, d_rec, rec_bytes, hipMemcpyDeviceToHost, h->cur));
-        if (features) HIPCHK(h, hipMemcpyAsync(features, d_feat, feat_bytes, hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipStreamSynchronize(h->cur));
-    }
-    return BK_OK;
+    Staging st(h, mem);
+    const auto s_states = st.in(states, sizeof(bk_state) * (size_t)n);
+    const auto s_sets = st.in(sets, sizeof(bk_fset) * (size_t)n);
+    const auto s_turn = st.in(turn_index, sizeof(int32_t) * (size_t)n);
+    const auto s_rec = st.out(rec, sizeof(bk_snapshot_rec) * 4 * (size_t)n);
+    const auto s_feat = st.out(features, sizeof(double) * BK_SNAPSHOT_COLUMNS * 4 * (size_t)n);
+    if (int rc = st.commit()) return rc;
+    SnapArgs a{s_states.dev(), s_sets.dev(), s_turn.dev(), n, max_turns, s_rec.dev(), s_feat.dev()};
+    BK_LAUNCH(h, k_snapshot, dim3(n), dim3(SNAP_WAVES * WAVE), a);
+    return st.finish();
 }
 
 int bk_winprob_model_size(void) { return (int)sizeof(bk_winprob_model); }
@@ -7212,39 +7123,18 @@ int bk_winprob_eval(bk_handle h, const bk_state* states, const bk_fset* sets, in
     if (n == 0) return BK_OK;
     HIPCHK(h, hipSetDevice(h->device));
     BK_IDLE(h, "bk_winprob_eval");
-    void *d_states, *d_sets, *d_turn = nullptr;
-    int rc = stage_in(h, states, sizeof(bk_state) * (size_t)n, mem, &d_states, &h->d_in, &h->d_in_cap);
-    if (rc) return rc;
-    rc = stage_in(h, sets, sizeof(bk_fset) * (size_t)n, mem, &d_sets, &h->d_fin, &h->d_fin_cap);
-    if (rc) return rc;
-    if (turn_index) {
-        rc = stage_in(h, turn_index, sizeof(int32_t) * (size_t)n, mem, &d_turn, &h->d_aux, &h->d_aux_cap);
-        if (rc) return rc;
-    }
-    const size_t prob_bytes = sizeof(double) * 4 * (size_t)n, logit_bytes = sizeof(double) * 12 * (size_t)n;
-    double *d_prob = prob, *d_logit = pair_logit;
-    uint8_t* d_status = status;
-    if (mem == BK_MEM_HOST) {  // one staging buffer: prob, the pair logits, then the status bytes
-        rc = grow(h, &h->d_out, &h->d_out_cap, prob_bytes + logit_bytes + (size_t)n);
-        if (rc) return rc;
-        d_prob = (double*)h->d_out;
-        d_logit = pair_logit ? (double*)((char*)h->d_out + prob_bytes) : nullptr;
-        d_status = (uint8_t*)h->d_out + prob_bytes + logit_bytes;
-    }
-    WinprobArgs a{{(const bk_state*)d_states, (const bk_fset*)d_sets, (const int32_t*)d_turn, n, max_turns, nullptr, nullptr},
-                  *model, d_prob, d_logit, d_status};
-    HIPCHK(h, mark_start(h));
-    h->last_kernel = "k_winprob";
-    hipLaunchKernelGGL(k_winprob, dim3(n), dim3(SNAP_WAVES * WAVE), 0, h->cur, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, mark_end(h));
-    if (mem == BK_MEM_HOST) {
-        HIPCHK(h, hipMemcpyAsync(prob, d_prob, prob_bytes, hipMemcpyDeviceToHost, h->cur));
-        if (pair_logit) HIPCHK(h, hipMemcpyAsync(pair_logit, d_logit, logit_bytes, hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipMemcpyAsync(status, d_status, (size_t)n, hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipStreamSynchronize(h->cur));
-    }
-    return BK_OK;
+    Staging st(h, mem);
+    const auto s_states = st.in(states, sizeof(bk_state) * (size_t)n);
+    const auto s_sets = st.in(sets, sizeof(bk_fset) * (size_t)n);
+    const auto s_turn = st.in(turn_index, sizeof(int32_t) * (size_t)n);
+    const auto s_prob = st.out(prob, sizeof(double) * 4 * (size_t)n);
+    const auto s_logit = st.out(pair_logit, sizeof(double) * 12 * (size_t)n);
+    const auto s_status = st.out(status, (size_t)n);
+    if (int rc = st.commit()) return rc;
+    WinprobArgs a{{s_states.dev(), s_sets.dev(), s_turn.dev(), n, max_turns, nullptr, nullptr},
+                  *model, s_prob.dev(), s_logit.dev(), s_status.dev()};
+    BK_LAUNCH(h, k_winprob, dim3(n), dim3(SNAP_WAVES * WAVE), a);
+    return st.finish();
 }
 
 int bk_arena_advance(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const bk_rollout_cfg* cfg,
@@ -7451,26 +7341,19 @@ int bk_debug_fastmcts_select(bk_handle h, int32_t n, const uint32_t* visits, con
         if (visits[j] == 0) return set_err(h, BK_EINVAL, "bk_debug_fastmcts_select: visits must be > 0%s", "");
     HIPCHK(h, hipSetDevice(h->device));
     BK_IDLE(h, "bk_debug_fastmcts_select");
-    const size_t bv = sizeof(uint32_t) * n, bt = sizeof(double) * n, bo = sizeof(int32_t) * (size_t)(pow_fix_rows + 1),
-                 be = sizeof(int32_t) * (size_t)(pow_fix_len + 1);
-    int rc = grow(h, &h->d_aux, &h->d_aux_cap, bt + bv + bo + be + 64);
-    if (rc) return rc;
-    char* p = (char*)h->d_aux;
-    double* d_t = (double*)p; p += bt;
-    uint32_t* d_v = (uint32_t*)p; p += bv;
-    int32_t* d_o = (int32_t*)p; p += bo;
-    int32_t* d_e = (int32_t*)p; p += be;
-    int32_t* d_out = (int32_t*)(((uintptr_t)p + 15) & ~(uintptr_t)15);
-    HIPCHK(h, hipMemcpyAsync(d_t, totals, bt, hipMemcpyHostToDevice, h->cur));
-    HIPCHK(h, hipMemcpyAsync(d_v, visits, bv, hipMemcpyHostToDevice, h->cur));
-    HIPCHK(h, hipMemcpyAsync(d_o, pow_fix_offsets, bo, hipMemcpyHostToDevice, h->cur));
-    if (pow_fix_len) HIPCHK(h, hipMemcpyAsync(d_e, pow_fix_entries, be - sizeof(int32_t), hipMemcpyHostToDevice, h->cur));
-    hipLaunchKernelGGL(k_fastmcts_select, dim3(1), dim3(WAVE), 0, h->cur, d_v, d_t, n, root_visits,
-                       2.0 * log_table[root_visits], exploration, PowFix{d_o, d_e, pow_fix_rows}, d_out);
+    Staging st(h, BK_MEM_HOST);
+    const auto s_totals = st.in(totals, sizeof(double) * (size_t)n);
+    const auto s_visits = st.in(visits, sizeof(uint32_t) * (size_t)n);
+    const auto s_fo = st.in(pow_fix_offsets, sizeof(int32_t) * (size_t)(pow_fix_rows + 1));
+    const auto s_fe = st.in(pow_fix_entries, sizeof(int32_t) * (size_t)pow_fix_len);  // absent when empty: never read
+    const auto s_best = st.out(out_best, sizeof(int32_t));
+    if (int rc = st.commit()) return rc;
+    // untimed: bk_last_kernel keeps naming the last timed launch
+    hipLaunchKernelGGL(k_fastmcts_select, dim3(1), dim3(WAVE), 0, h->cur, s_visits.dev(), s_totals.dev(), n, root_visits,
+                       2.0 * log_table[root_visits], exploration, PowFix{s_fo.dev(), s_fe.dev(), pow_fix_rows},
+                       s_best.dev());
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out_best, d_out, sizeof(int32_t), hipMemcpyDeviceToHost, h->cur));
-    HIPCHK(h, hipStreamSynchronize(h->cur));
-    return BK_OK;
+    return st.finish();
 }
 
 int bk_fastmcts(bk_handle h, int32_t n_games, const int32_t* legal_offset, const int32_t* iterations,
@@ -7487,20 +7370,7 @@ int bk_fastmcts(bk_handle h, int32_t n_games, const int32_t* legal_offset, const
     if (n_games == 0) return BK_OK;
     HIPCHK(h, hipSetDevice(h->device));
     BK_IDLE(h, "bk_fastmcts");
-    const size_t b_off = sizeof(int32_t) * (size_t)(n_games + 1), b_it = sizeof(int32_t) * (size_t)n_games,
-                 b_base = sizeof(double) * (size_t)n_games, b_mt = sizeof(uint32_t) * 625 * (size_t)n_games,
-                 b_log = sizeof(double) * (size_t)log_len, b_out = sizeof(bk_fastmcts_out) * (size_t)n_games,
-                 b_fo = sizeof(int32_t) * (size_t)(pow_fix_rows + 1), b_fe = sizeof(int32_t) * (size_t)(pow_fix_len + 1);
-    const int32_t* d_off = legal_offset;
-    const int32_t* d_it = iterations;
-    const double* d_base = base;
-    uint32_t* d_mt = mt_state;
-    const double* d_log = log_table;
-    const int32_t* d_fo = pow_fix_offsets;
-    const int32_t* d_fe = pow_fix_entries;
-    bk_fastmcts_out* d_out = out;
-    int32_t* d_vis = visits_out;
-    int32_t n_legal_total = 0;
+    int32_t n_legal_total = 0;  // read from the caller's arrays in host memory only (device mode stages nothing)
     if (mem == BK_MEM_HOST) {
         if (legal_offset[0] != 0) return set_err(h, BK_EINVAL, "bk_fastmcts: legal_offset[0] must be 0%s", "");
         for (int32_t i = 0; i < n_games; ++i)
@@ -7508,53 +7378,26 @@ int bk_fastmcts(bk_handle h, int32_t n_games, const int32_t* legal_offset, const
                 return set_err(h, BK_EINVAL, "bk_fastmcts: bad legal_offset/iterations%s", "");
         n_legal_total = legal_offset[n_games];
     }
-    if (mem == BK_MEM_HOST) {
-        // one staging buffer, 16-byte aligned sections
-        auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-        const size_t tot = al(b_off) + al(b_it) + al(b_base) + al(b_mt) + al(b_log) + al(b_fo) + al(b_fe);
-        int rc = grow(h, &h->d_in, &h->d_in_cap, tot);
-        if (rc) return rc;
-        rc = grow(h, &h->d_out, &h->d_out_cap, b_out);
-        if (rc) return rc;
-        char* p = (char*)h->d_in;
-        HIPCHK(h, hipMemcpyAsync(p, legal_offset, b_off, hipMemcpyHostToDevice, h->cur)); d_off = (const int32_t*)p; p += al(b_off);
-        HIPCHK(h, hipMemcpyAsync(p, iterations, b_it, hipMemcpyHostToDevice, h->cur)); d_it = (const int32_t*)p; p += al(b_it);
-        HIPCHK(h, hipMemcpyAsync(p, base, b_base, hipMemcpyHostToDevice, h->cur)); d_base = (const double*)p; p += al(b_base);
-        HIPCHK(h, hipMemcpyAsync(p, mt_state, b_mt, hipMemcpyHostToDevice, h->cur)); d_mt = (uint32_t*)p; p += al(b_mt);
-        HIPCHK(h, hipMemcpyAsync(p, log_table, b_log, hipMemcpyHostToDevice, h->cur)); d_log = (const double*)p; p += al(b_log);
-        HIPCHK(h, hipMemcpyAsync(p, pow_fix_offsets, b_fo, hipMemcpyHostToDevice, h->cur)); d_fo = (const int32_t*)p; p += al(b_fo);
-        if (pow_fix_len)
-            HIPCHK(h, hipMemcpyAsync(p, pow_fix_entries, b_fe - sizeof(int32_t), hipMemcpyHostToDevice, h->cur));
-        d_fe = (const int32_t*)p;
-        d_out = (bk_fastmcts_out*)h->d_out;
-        if (visits_out) {
-            rc = grow(h, &h->d_aux, &h->d_aux_cap, sizeof(int32_t) * (size_t)n_legal_total + 4);
-            if (rc) return rc;
-            d_vis = (int32_t*)h->d_aux;
-        }
-    }
+    const size_t n = (size_t)n_games;
+    Staging st(h, mem);
+    const auto s_off = st.in(legal_offset, sizeof(int32_t) * (n + 1));
+    const auto s_it = st.in(iterations, sizeof(int32_t) * n);
+    const auto s_base = st.in(base, sizeof(double) * n);
+    const auto s_mt = st.inout(mt_state, sizeof(uint32_t) * 625 * n);
+    const auto s_log = st.in(log_table, sizeof(double) * (size_t)log_len);
+    const auto s_fo = st.in(pow_fix_offsets, sizeof(int32_t) * (size_t)(pow_fix_rows + 1));
+    const auto s_fe = st.in(pow_fix_entries, sizeof(int32_t) * (size_t)pow_fix_len);  // absent when empty: never read
+    const auto s_out = st.out(out, sizeof(bk_fastmcts_out) * n);
+    const auto s_vis = st.out(visits_out, sizeof(int32_t) * (size_t)n_legal_total);
+    if (int rc = st.commit()) return rc;
     HIPCHK(h, hipMemsetAsync(h->d_counter, 0, 2 * sizeof(uint32_t), h->cur));  // [2] is sticky
-    FastMctsArgs a{n_games, d_off, d_it, d_base, d_mt, d_log, log_len, PowFix{d_fo, d_fe, pow_fix_rows}, exploration,
-                   d_out, d_vis,
+    FastMctsArgs a{n_games, s_off.dev(), s_it.dev(), s_base.dev(), s_mt.dev(), s_log.dev(), log_len,
+                   PowFix{s_fo.dev(), s_fe.dev(), pow_fix_rows}, exploration, s_out.dev(), s_vis.dev(),
                    h->d_counter + 1};
-    HIPCHK(h, mark_start(h));
-    h->last_kernel = "k_fastmcts";
-    hipLaunchKernelGGL(k_fastmcts, dim3(n_games), dim3(WAVE), 0, h->cur, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, mark_end(h));
-    if (mem == BK_MEM_HOST) {
-        uint32_t ctr[4];
-        HIPCHK(h, hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipMemcpyAsync(mt_state, d_mt, b_mt, hipMemcpyDeviceToHost, h->cur));
-        if (visits_out && n_legal_total > 0)
-            HIPCHK(h, hipMemcpyAsync(visits_out, d_vis, sizeof(int32_t) * (size_t)n_legal_total,
-                                     hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipMemcpyAsync(ctr, h->d_counter, sizeof ctr, hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipStreamSynchronize(h->cur));
-        if (int rc = clear_own_sticky(h, ctr[2], BK_STICKY_FASTMCTS)) return rc;  // reported here
-        if (ctr[1]) return set_err(h, BK_EINVAL, "bk_fastmcts: too many children or log table too short%s", "");
-    }
-    return BK_OK;
+    BK_LAUNCH(h, k_fastmcts, dim3(n_games), dim3(WAVE), a);
+    if (mem == BK_MEM_DEVICE) return BK_OK;  // an error stays sticky for bk_synchronize
+    return finish_guarded(h, st, BK_STICKY_FASTMCTS, BK_EINVAL,
+                          "bk_fastmcts: too many children or log table too short%s");
 }
 
 int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const uint8_t* players,
@@ -7593,52 +7436,41 @@ int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const 
     BK_IDLE(h, "bk_mcts");
     const size_t n = (size_t)n_games, ttc = cfg->use_tt ? (size_t)cfg->tt_cap : 0;
     const size_t it = (size_t)cfg->iterations;
-    struct Sec { const void* host; size_t bytes; int dir; void* dev; };  // dir: 1 in, 2 out, 3 in+out
-    Sec sec[] = {
-        {roots, sizeof(bk_state) * n, 1, nullptr},
-        {root_sets, sizeof(bk_fset) * n, 1, nullptr},
-        {players, n, 1, nullptr},
-        {root_hash, sizeof(uint64_t) * n, 1, nullptr},
-        {zobrist, sizeof(uint64_t) * MC_ZOB * (size_t)n_zobrist, 1, nullptr},
-        {zobrist_index, sizeof(int32_t) * n, 1, nullptr},
-        {mt_state, sizeof(uint32_t) * 625 * n, 3, nullptr},
-        {tt_keys, sizeof(uint64_t) * ttc * n, 3, nullptr},
-        {tt_vals, sizeof(double) * ttc * n, 3, nullptr},
-        {tt_count, cfg->use_tt ? sizeof(int32_t) * n : 0, 3, nullptr},
-        {log_table, sizeof(double) * (size_t)log_len, 1, nullptr},
-        {nodes, sizeof(bk_mcts_node) * (size_t)cfg->node_cap * n, cfg->resume ? 3 : 2, nullptr},
-        {rewards, sizeof(double) * it * n, cfg->resume ? 3 : 2, nullptr},
-        {hit_flags, it * n, cfg->resume ? 3 : 2, nullptr},
-        {out, sizeof(bk_mcts_out) * n, cfg->resume ? 3 : 2, nullptr},
-    };
-    const int NSEC = (int)(sizeof sec / sizeof sec[0]);
-    const int NODES = 11;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t tot = 0;
-    for (int i = 0; i < NSEC; ++i) {
-        const bool staged = mem == BK_MEM_HOST || (i == NODES && nodes == nullptr);
-        if (staged && sec[i].bytes && (sec[i].host || i == NODES)) tot += al(sec[i].bytes);
-    }
-    int rc = grow(h, &h->d_mc, &h->d_mc_cap, tot + 256);
+    const int io = cfg->resume ? Staging::INOUT : Staging::OUT;  // a resumed search reads what the last one left
+    const size_t node_bytes = sizeof(bk_mcts_node) * (size_t)cfg->node_cap * n;
+    Staging st(h, mem);
+    const auto s_roots = st.in(roots, sizeof(bk_state) * n);
+    const auto s_sets = st.in(root_sets, sizeof(bk_fset) * n);
+    const auto s_players = st.in(players, n);
+    const auto s_hash = st.in(root_hash, sizeof(uint64_t) * n);
+    const auto s_zob = st.in(zobrist, sizeof(uint64_t) * MC_ZOB * (size_t)n_zobrist);
+    const auto s_zidx = st.in(zobrist_index, sizeof(int32_t) * n);
+    const auto s_mt = st.inout(mt_state, sizeof(uint32_t) * 625 * n);
+    const auto s_ttk = st.inout(tt_keys, sizeof(uint64_t) * ttc * n);
+    const auto s_ttv = st.inout(tt_vals, sizeof(double) * ttc * n);
+    const auto s_ttn = st.inout(tt_count, cfg->use_tt ? sizeof(int32_t) * n : 0);
+    const auto s_log = st.in(log_table, sizeof(double) * (size_t)log_len);
+    const auto s_nodes = st.add(nodes, node_bytes, io);
+    const auto s_rewards = st.add(rewards, sizeof(double) * it * n, io);
+    const auto s_hits = st.add(hit_flags, it * n, io);
+    const auto s_out = st.add(out, sizeof(bk_mcts_out) * n, io);
+    int rc = st.commit();
     if (rc) return rc;
-    char* p = (char*)h->d_mc;
-    for (int i = 0; i < NSEC; ++i) {
-        const bool staged = mem == BK_MEM_HOST || (i == NODES && nodes == nullptr);
-        if (!staged) { sec[i].dev = const_cast<void*>(sec[i].host); continue; }
-        if (!sec[i].bytes || (!sec[i].host && i != NODES)) { sec[i].dev = nullptr; continue; }
-        sec[i].dev = p;
-        if ((sec[i].dir & 1) && sec[i].host)
-            HIPCHK(h, hipMemcpyAsync(p, sec[i].host, sec[i].bytes, hipMemcpyHostToDevice, h->cur));
-        p += al(sec[i].bytes);
+    Buf* const wb = h->buf;  // the work buffers, by bk_handle_s's names
+    bk_mcts_node* d_nodes = s_nodes.dev();
+    if (!nodes) {  // no caller's pool: the handle's, in either memory mode
+        rc = grow(h, wb[bk_handle_s::NODES], node_bytes);
+        if (rc) return rc;
+        d_nodes = (bk_mcts_node*)wb[bk_handle_s::NODES].p;
     }
-    if (!root_hash) {  // ZobristHash.hash_board of every root, on the device
-        rc = grow(h, &h->d_rh, &h->d_rh_cap, sizeof(uint64_t) * n);
+    const uint64_t* d_hash = s_hash.dev();
+    if (!root_hash) {  // ZobristHash.hash_board of every root, on the device (untimed)
+        rc = grow(h, wb[bk_handle_s::RH], sizeof(uint64_t) * n);
         if (rc) return rc;
         hipLaunchKernelGGL(k_root_hash, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->cur,
-                           (const bk_state*)sec[0].dev, (const uint64_t*)sec[4].dev, (const int32_t*)sec[5].dev,
-                           (uint64_t*)h->d_rh, n_games);
+                           s_roots.dev(), s_zob.dev(), s_zidx.dev(), (uint64_t*)wb[bk_handle_s::RH].p, n_games);
         HIPCHK(h, hipGetLastError());
-        sec[3].dev = h->d_rh;
+        d_hash = (const uint64_t*)wb[bk_handle_s::RH].p;
     }
     // persistent grid: every resident slot pulls whole searches from the counter
     const bool heur = cfg->rollout_policy == BK_MCTS_ROLLOUT_HEURISTIC;
@@ -7669,9 +7501,9 @@ int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const 
     if (blocks > need) blocks = need;
     if (blocks < 1) blocks = 1;
     const uint32_t nslots = (uint32_t)blocks * per_block;
-    rc = grow(h, &h->d_slab, &h->d_slab_cap, sizeof(uint32_t) * SLAB_WORDS * (size_t)nslots);
+    rc = grow(h, wb[bk_handle_s::SLAB], sizeof(uint32_t) * SLAB_WORDS * (size_t)nslots);
     if (rc) return rc;
-    rc = grow(h, &h->d_mclane, &h->d_mclane_cap, sizeof(McLane) * (size_t)nslots);
+    rc = grow(h, wb[bk_handle_s::MCLANE], sizeof(McLane) * (size_t)nslots);
     if (rc) return rc;
     int khz = 0;
     HIPCHK(h, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->device));
@@ -7683,75 +7515,53 @@ int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const 
     int32_t tree_batch = MC_TREE_BATCH;
     tree_batch = (int32_t)tune_or(h, BK_TUNE_TREE_BATCH, tree_batch);
     if (tree_batch < 1) tree_batch = 1;
-    MctsArgs a{(const bk_state*)sec[0].dev, (const bk_fset*)sec[1].dev, (const uint8_t*)sec[2].dev,
-               (const uint64_t*)sec[3].dev, n_games, *cfg, (const uint64_t*)sec[4].dev,
-               (const int32_t*)sec[5].dev, (uint32_t*)sec[6].dev, (uint64_t*)sec[7].dev, (double*)sec[8].dev,
-               (int32_t*)sec[9].dev, (const double*)sec[10].dev, log_len, (bk_mcts_node*)sec[11].dev,
-               (double*)sec[12].dev, (uint8_t*)sec[13].dev, (bk_mcts_out*)sec[14].dev,
-               (uint32_t*)h->d_slab, (McLane*)h->d_mclane, h->d_counter, steps,
-               (uint64_t)cfg->time_limit_us * (uint64_t)khz / 1000u, tree_batch, spread, 1, 1};
+    MctsArgs a{s_roots.dev(), s_sets.dev(), s_players.dev(), d_hash, n_games, *cfg, s_zob.dev(), s_zidx.dev(),
+               s_mt.dev(), s_ttk.dev(), s_ttv.dev(), s_ttn.dev(), s_log.dev(), log_len, d_nodes, s_rewards.dev(),
+               s_hits.dev(), s_out.dev(), (uint32_t*)wb[bk_handle_s::SLAB].p, (McLane*)wb[bk_handle_s::MCLANE].p,
+               h->d_counter, steps, (uint64_t)cfg->time_limit_us * (uint64_t)khz / 1000u, tree_batch, spread, 1, 1};
     a.diag = h->d_diag;
     a.launch_seq = ++h->mcts_launches;
     a.state_rows = (cfg->flags & BK_MCTS_STATE_ROWS) ? 1 : 0;
     a.done = h->mcts_done;
     if (a.state_rows) {  // the searches work on copies of their agents' MT rows
-        rc = grow(h, &h->d_mtwork, &h->d_mtwork_cap, sizeof(uint32_t) * (FM_N + 1) * n);
+        rc = grow(h, wb[bk_handle_s::MTWORK], sizeof(uint32_t) * (FM_N + 1) * n);
         if (rc) return rc;
         a.mt_rows = a.mt;
-        a.mt = (uint32_t*)h->d_mtwork;
+        a.mt = (uint32_t*)wb[bk_handle_s::MTWORK].p;
     }
     {
         const size_t sb = sizeof(uint32_t) * (((size_t)n_games + 31) / 32 + 1);
-        rc = grow(h, &h->d_started, &h->d_started_cap, sb);
+        rc = grow(h, wb[bk_handle_s::STARTED], sb);
         if (rc) return rc;
-        HIPCHK(h, hipMemsetAsync(h->d_started, 0, sb, h->cur));
-        a.started = (uint32_t*)h->d_started;
+        a.started = (uint32_t*)wb[bk_handle_s::STARTED].p;
+        HIPCHK(h, hipMemsetAsync(a.started, 0, sb, h->cur));
     }
     a.coop_walk = (int)tune_or(h, BK_TUNE_COOP_WALK, a.coop_walk);
     a.coop_balanced = (int)tune_or(h, BK_TUNE_COOP_BAL, a.coop_balanced);
     // spread 2: the idle odd lane of each pair splits the even lane's stencil (k_mcts_pair)
     const bool pair = tune_or(h, BK_TUNE_MCTS_PAIR, 1) != 0;
-    HIPCHK(h, mark_start(h));
     if (coop && heur) {
-        h->last_kernel = "k_mcts_coop_h";
         a.kernel_id = BK_DIAG_K_COOP_H;
-        hipLaunchKernelGGL(k_mcts_coop_h, dim3(blocks), dim3(blk), 0, h->cur, a);
+        BK_LAUNCH(h, k_mcts_coop_h, dim3(blocks), dim3(blk), a);
     } else if (coop) {
-        h->last_kernel = "k_mcts_coop";
         a.kernel_id = BK_DIAG_K_COOP;
-        hipLaunchKernelGGL(k_mcts_coop, dim3(blocks), dim3(blk), 0, h->cur, a);
+        BK_LAUNCH(h, k_mcts_coop, dim3(blocks), dim3(blk), a);
     } else if (heur) {
-        h->last_kernel = "k_mcts_h";
         a.kernel_id = BK_DIAG_K_H;
-        hipLaunchKernelGGL(k_mcts_h, dim3(blocks), dim3(HBLOCK), 0, h->cur, a);
+        BK_LAUNCH(h, k_mcts_h, dim3(blocks), dim3(HBLOCK), a);
     } else if (spread == 2 && pair) {
-        h->last_kernel = "k_mcts_pair";
         a.kernel_id = BK_DIAG_K_PAIR;
-        hipLaunchKernelGGL(k_mcts_pair, dim3(blocks), dim3(BLOCK), 0, h->cur, a);
+        BK_LAUNCH(h, k_mcts_pair, dim3(blocks), dim3(BLOCK), a);
     } else {
-        h->last_kernel = "k_mcts";
-        hipLaunchKernelGGL(k_mcts, dim3(blocks), dim3(BLOCK), 0, h->cur, a);
+        BK_LAUNCH(h, k_mcts, dim3(blocks), dim3(BLOCK), a);
     }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, mark_end(h));
     if (mem == BK_MEM_DEVICE && (cfg->flags & BK_MCTS_ASYNC)) {  // errors: bk_synchronize
         h->busy = true;  // the running search owns the scratch until then
         h->busy_stream = h->cur;
         return BK_OK;
     }
-    uint32_t ctr[4];
-    if (mem == BK_MEM_HOST) {
-        for (int i = 0; i < NSEC; ++i)
-            if ((sec[i].dir & 2) && sec[i].host && sec[i].bytes)
-                HIPCHK(h, hipMemcpyAsync(const_cast<void*>(sec[i].host), sec[i].dev, sec[i].bytes,
-                                         hipMemcpyDeviceToHost, h->cur));
-    }
-    HIPCHK(h, hipMemcpyAsync(ctr, h->d_counter, sizeof ctr, hipMemcpyDeviceToHost, h->cur));
-    HIPCHK(h, hipStreamSynchronize(h->cur));
-    if (int rc = clear_own_sticky(h, ctr[2], BK_STICKY_GUARD)) return rc;  // reported here
-    if (ctr[1]) return set_err(h, BK_EOVERFLOW, "bk_mcts: step guard tripped%s", "");
-    if (int rc = take_diag(h)) return rc;  // a search broke a tree invariant (mc_diag)
-    return BK_OK;
+    rc = finish_guarded(h, st, BK_STICKY_GUARD, BK_EOVERFLOW, "bk_mcts: step guard tripped%s");
+    return rc ? rc : take_diag(h);  // a search broke a tree invariant (mc_diag)
 }
 
 }  // extern "C"
