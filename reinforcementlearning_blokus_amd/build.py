@@ -57,7 +57,12 @@ _NO_MLICM = ("-mllvm", "-disable-machine-licm")
 # lane-pair scan of k_mcts_pair pays per class, so it takes the unsplit classes with
 # their shared flags; k_rollout_fr_h has no measurement and keeps the unflagged code
 # (profiles/r11)
-UNIT_FLAGS = {"rollout_fr": _NO_MLICM, "coop": _NO_MLICM, "coop_h": _NO_MLICM,
+# The playout kernels and k_mcts count the stencil in phases and rebuild the second
+# plane between them (BK_STENCIL_MUX), each on an A/B of its own; k_mcts_h measured no
+# different with it and the dense-mask kernels of config 2 do not go through the code it
+# changes, so those units keep their lists (profiles/r13)
+_MUX = ("-DBK_STENCIL_MUX",)
+UNIT_FLAGS = {"rollout_fr": _NO_MLICM + _MUX, "rollout": _MUX, "mcts": _MUX, "coop": _NO_MLICM, "coop_h": _NO_MLICM,
               "mcts_pair": ("-DBK_STENCIL_COMMON",), "rollout_frh": ("-DBK_STENCIL_PLAIN",)}
 
 

@@ -135,6 +135,9 @@ typedef uint4 bk_u4_alias __attribute__((may_alias));
 __constant__ uint32_t kInfo[BK_NUM_ORIENTS] = BK_ORIENT_INFO_INIT;
 __constant__ uint32_t kCells[BK_NUM_ORIENTS][5] = BK_ORIENT_CELLS_INIT;
 __constant__ uint32_t kClass[BK_NUM_ORIENTS][2] = BK_CLASS_TABLE_INIT;
+#ifdef BK_STENCIL_MUX
+__constant__ uint32_t kClassMux[BK_NUM_ORIENTS][2] = BK_CLASS_TABLE_MUX_INIT;  // the per-phase lists' own table
+#endif
 
 // frontier_ops: per orientation, bit 9 q + o set iff q < n and op o of cell q is the first
 // op of its kind (add / discard) on its cell relative to the anchor -- later ones are
@@ -295,6 +298,10 @@ __device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
 // -DBK_STENCIL_COMMON scans the unsplit classes with the flags their entries share
 // (count_class_pair pays per class: an odd sub-class wastes half a scan);
 // -DBK_STENCIL_PLAIN scans them with no flag, which is the code from before the flags.
+// -DBK_STENCIL_MUX (movegen_counts, all_rows; every other scan keeps the default list)
+// scans the orientations in phases, BK_CLASS_LIST_MUX_P / _Q / _T / _U over kClassMux,
+// and rebuilds the second plane between them (mux_plane_*, BK_MUX_PASS): each
+// orientation sits in the phase whose plane covers it with the fewest ORs and shifts.
 #if defined(BK_STENCIL_PLAIN)
 #define BK_CLASS_LIST(X) BK_CLASS_LIST_PLAIN(X)
 #elif defined(BK_STENCIL_COMMON)
@@ -397,6 +404,77 @@ struct StencilClass {
     }
 };
 
+#ifdef BK_STENCIL_MUX
+// The second plane of the next phase, written over the previous one's rows (kind 1 of
+// the BK_CLASS_LIST_MUX_* tokens).  Every input is a plane row, so left to the optimizer
+// the new rows are computed before the earlier phases' classes and 40 more VGPRs stay
+// live across the whole stencil; as volatile asm they are made where they are written,
+// after the last class that reads the old plane.
+// t: the horizontal triple B | B >> 1 | B >> 2 (B's bits 30, 31 (OFFBOARD) absorb C's
+// bits 0, 1), from the pair plane when that is the plane it replaces
+__device__ __forceinline__ void mux_plane_t(Planes& Q) {
+#pragma unroll
+    for (int R = 0; R < 20; ++R) {
+        uint64_t s;
+        uint32_t lo, hi;
+        asm volatile("v_lshrrev_b64 %0, 2, %1" : "=v"(s) : "v"(Q.BC[R]));
+        asm volatile("v_or_b32 %0, %1, %2" : "=v"(lo) : "v"((uint32_t)Q.BCP[R]), "v"((uint32_t)s));
+        asm volatile("v_or_b32 %0, %1, %2" : "=v"(hi) : "v"((uint32_t)(Q.BCP[R] >> 32)), "v"((uint32_t)(s >> 32)));
+        Q.BCP[R] = ((uint64_t)hi << 32) | lo;
+    }
+}
+// q: the 2 x 2 square p[R] | p[R + 1], in place over the pair plane (row 19: never a top)
+__device__ __forceinline__ void mux_plane_q(Planes& Q) {
+#pragma unroll
+    for (int R = 0; R < 19; ++R) {
+        uint32_t lo, hi;
+        asm volatile("v_or_b32 %0, %1, %2" : "=v"(lo) : "v"((uint32_t)Q.BCP[R]), "v"((uint32_t)Q.BCP[R + 1]));
+        asm volatile("v_or_b32 %0, %1, %2" : "=v"(hi) : "v"((uint32_t)(Q.BCP[R] >> 32)), "v"((uint32_t)(Q.BCP[R + 1] >> 32)));
+        Q.BCP[R] = ((uint64_t)hi << 32) | lo;
+    }
+}
+// t after q: the pair plane is gone, so from the B/C rows
+__device__ __forceinline__ void mux_plane_t_bc(Planes& Q) {
+#pragma unroll
+    for (int R = 0; R < 20; ++R) {
+        uint64_t s1, s2;
+        uint32_t lo, hi;
+        asm volatile("v_lshrrev_b64 %0, 1, %1" : "=v"(s1) : "v"(Q.BC[R]));
+        asm volatile("v_lshrrev_b64 %0, 2, %1" : "=v"(s2) : "v"(Q.BC[R]));
+        asm volatile("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xfe"
+                     : "=v"(lo) : "v"((uint32_t)Q.BC[R]), "v"((uint32_t)s1), "v"((uint32_t)s2));
+        asm volatile("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xfe"
+                     : "=v"(hi) : "v"((uint32_t)(Q.BC[R] >> 32)), "v"((uint32_t)(s1 >> 32)), "v"((uint32_t)(s2 >> 32)));
+        Q.BCP[R] = ((uint64_t)hi << 32) | lo;
+    }
+}
+// u: the vertical triple B[R] | B[R + 1] | B[R + 2]; a row past 19 is absent (no
+// orientation has a triple's top there)
+__device__ __forceinline__ void mux_plane_u(Planes& Q) {
+#pragma unroll
+    for (int R = 0; R < 20; ++R) {
+        const uint64_t a = Q.BC[R], b = Q.BC[R < 19 ? R + 1 : R], c = Q.BC[R < 18 ? R + 2 : R];
+        uint32_t lo, hi;
+        asm volatile("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xfe"
+                     : "=v"(lo) : "v"((uint32_t)a), "v"((uint32_t)b), "v"((uint32_t)c));
+        asm volatile("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xfe"
+                     : "=v"(hi) : "v"((uint32_t)(a >> 32)), "v"((uint32_t)(b >> 32)), "v"((uint32_t)(c >> 32)));
+        Q.BCP[R] = ((uint64_t)hi << 32) | lo;
+    }
+}
+// One pass over the phases: X expands a class, Q is the pass's own copy of the planes.
+// q comes right after p, whose rows it is made of; a header generated without the q
+// phase (tools/gen_tables.py BK_GEN_MUX=p,t,u) gives the three-phase pass.
+#ifdef BK_CLASS_LIST_MUX_Q
+#define BK_MUX_PASS(X, Q) \
+    BK_CLASS_LIST_MUX_P(X) mux_plane_q(Q); BK_CLASS_LIST_MUX_Q(X) mux_plane_t_bc(Q); \
+    BK_CLASS_LIST_MUX_T(X) mux_plane_u(Q); BK_CLASS_LIST_MUX_U(X)
+#else
+#define BK_MUX_PASS(X, Q) \
+    BK_CLASS_LIST_MUX_P(X) mux_plane_t(Q); BK_CLASS_LIST_MUX_T(X) mux_plane_u(Q); BK_CLASS_LIST_MUX_U(X)
+#endif
+#endif
+
 // Per-orientation counts in LDS, 10 bits each, three per dword: orientation g lives in
 // dword g / 3 at bit 10 * (g % 3), laid out [dword][lane] (31 dwords per lane).  The
 // rollout zeroes a lane's dwords before each movegen and ds_add_u32's every count in
@@ -449,13 +527,14 @@ struct StencilClass {
 // Orientations whose piece no lane of the wave may still play are skipped with a
 // uniform branch.
 template <bool STORE, int H, int... T>
-__device__ __forceinline__ uint32_t count_class(int i0, int i1, const Planes& P, uint32_t avail, uint32_t* cl) {
+__device__ __forceinline__ uint32_t count_class(int i0, int i1, const Planes& P, uint32_t avail, uint32_t* cl,
+                                                const uint32_t (*tab)[2] = kClass) {
     uint32_t total = 0;
-    uint32_t w0 = kClass[i0][0], w1 = kClass[i0][1];
+    uint32_t w0 = tab[i0][0], w1 = tab[i0][1];
 #pragma unroll 1
     for (int i = i0; i < i1; ++i) {
         const int nx = i + 1 < i1 ? i + 1 : i;  // prefetch the next entry
-        const uint32_t n0 = kClass[nx][0], n1 = kClass[nx][1];
+        const uint32_t n0 = tab[nx][0], n1 = tab[nx][1];
         const uint32_t piece = w0 & 0xFFu;
         const int g = (int)(w0 >> 8);
         const bool av = (avail >> (piece - 1u)) & 1u;
@@ -528,20 +607,30 @@ __device__ __forceinline__ uint32_t movegen_counts(const Planes& P, uint32_t ava
         BK_CLASS_LIST(BK_COUNT_CLASS)
 #undef BK_COUNT_CLASS
     } else {
+#ifdef BK_STENCIL_MUX
+#define BK_COUNT_CLASS(i0, i1, H, ...) t += count_class<STORE, H, __VA_ARGS__>(i0 + tb0, i1 + tb0, Q, avail, cl, kClassMux); \
+        asm volatile("" : "+v"(t));
+        Planes Q;  // B/C rows and the phase's second plane (P's own rows stay as they are)
+#pragma unroll
+        for (int R = 0; R < 20; ++R) { Q.BC[R] = P.BC[R]; Q.BCP[R] = P.BCP[R]; }
+        BK_MUX_PASS(BK_COUNT_CLASS, Q)
+#undef BK_COUNT_CLASS
+#else
 #define BK_COUNT_CLASS(i0, i1, H, ...) t += count_class<STORE, H, __VA_ARGS__>(i0 + tb0, i1 + tb0, P, avail, cl); \
         asm volatile("" : "+v"(t));
         BK_CLASS_LIST(BK_COUNT_CLASS)
 #undef BK_COUNT_CLASS
+#endif
     }
     return t;
 }
 
 // Dense legal rows of every orientation (k_movegen): calls f(g, piece, ok[20])
 template <int H, int... T, typename F>
-__device__ __forceinline__ void rows_class(int i0, int i1, const Planes& P, F&& f) {
+__device__ __forceinline__ void rows_class(int i0, int i1, const Planes& P, F&& f, const uint32_t (*tab)[2] = kClass) {
 #pragma unroll 1
     for (int i = i0; i < i1; ++i) {
-        const uint32_t w0 = kClass[i][0], w1 = kClass[i][1];
+        const uint32_t w0 = tab[i][0], w1 = tab[i][1];
         uint32_t ok[20];
 #pragma unroll
         for (int r = 0; r < 20; ++r) ok[r] = 0u;
@@ -552,9 +641,18 @@ __device__ __forceinline__ void rows_class(int i0, int i1, const Planes& P, F&& 
 
 template <typename F>
 __device__ __forceinline__ void all_rows(const Planes& P, F&& f) {
+#ifdef BK_STENCIL_MUX
+#define BK_ROWS_CLASS(i0, i1, H, ...) rows_class<H, __VA_ARGS__>(i0, i1, Q, f, kClassMux);
+    Planes Q;
+#pragma unroll
+    for (int R = 0; R < 20; ++R) { Q.BC[R] = P.BC[R]; Q.BCP[R] = P.BCP[R]; }
+    BK_MUX_PASS(BK_ROWS_CLASS, Q)
+#undef BK_ROWS_CLASS
+#else
 #define BK_ROWS_CLASS(i0, i1, H, ...) rows_class<H, __VA_ARGS__>(i0, i1, P, f);
     BK_CLASS_LIST(BK_ROWS_CLASS)
 #undef BK_ROWS_CLASS
+#endif
 }
 
 // orientation holding the k-th legal move (naive order: g ascending) and its rank in it.

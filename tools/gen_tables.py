@@ -8,7 +8,8 @@ offsets were already seen is dropped.  The global orientation id g runs piece-ma
 (piece 1 first), orientation index ascending: g order == reference list order.
 
 tests/test_stencil_table.py checks the committed header against this output and its
-stencil class lists against the placement rule.
+stencil class lists against the placement rule; tests/test_stencil_mux_table.py does the
+same for the per-phase lists (`--mux-stats` prints their static op counts).
 """
 import os
 
@@ -204,6 +205,130 @@ def render_classes(table):
     return lines
 
 
+# Per-phase second planes (-DBK_STENCIL_MUX).  The class loop is straight-line code and
+# the order of the orientations is free, so the 20 rows of the second plane can be
+# rebuilt between groups of classes; each orientation is scanned in the phase whose
+# plane covers it most cheaply.  A phase's kind-1 term is one placement of its shape:
+#   p  horizontal pair    B | B >> 1             (the plane of the lists above)
+#   t  horizontal triple  B | B >> 1 | B >> 2
+#   u  vertical triple    B[R] | B[R + 1] | B[R + 2]
+#   q  2 x 2 square       p[R] | p[R + 1]
+MUX_SHAPES = {"p": ((0, 0), (0, 1)), "t": ((0, 0), (0, 1), (0, 2)), "u": ((0, 0), (1, 0), (2, 0)),
+              "q": ((0, 0), (0, 1), (1, 0), (1, 1))}
+# MUX_PHASES is the order in which a tie between phases is settled (the earlier one); the
+# kernel scans q right after p, whose rows it is made of.  BK_GEN_MUX overrides the phases
+# for one regeneration ("p,t,u": the pass without q, for an A/B).
+MUX_PHASES = tuple(os.environ.get("BK_GEN_MUX", "p,t,u,q").split(","))
+MUX_MAX_COL = 3  # a shift of <= 3 moves C bits only into B's off-board bits; w1 keeps 3 bits per term
+
+
+def mux_covers(cells, shape):
+    """The cheapest covers of an orientation by single cells and placements of one extra
+    shape, every term at a column <= MUX_MAX_COL and one of them at column 0.  Cost per
+    anchor row: one OR-type op per term and one shift per term at a non-zero column;
+    ties go to fewer terms.  Returns (cost, [terms, ...]): every cover of that cost and
+    length, each as [(kind, d, c)] in class order (a column-0 term first, the rest by
+    (d, kind, c)) and once per choice of the first term; kind 1 = the shape.  None where
+    the rules leave no cover (the horizontal I5 with singles and u)."""
+    import itertools
+    cs = set(cells)
+    target = frozenset(cells)
+    P = [(0, r, c, frozenset([(r, c)])) for r, c in cells if c <= MUX_MAX_COL]
+    for r, c in cells:
+        sub = frozenset((r + dr, c + dc) for dr, dc in MUX_SHAPES[shape])
+        if c <= MUX_MAX_COL and sub <= cs:
+            P.append((1, r, c, sub))
+    best, covers = None, []
+    for k in range(1, 6):
+        for combo in itertools.combinations(P, k):
+            if frozenset().union(*[x[3] for x in combo]) != target or all(x[2] for x in combo):
+                continue
+            terms = sorted(((x[0], x[1], x[2]) for x in combo), key=lambda t: (t[1], t[0], t[2]))
+            rank = (k + sum(1 for t in terms if t[2]), k)
+            if best is None or rank < best:
+                best, covers = rank, []
+            if rank == best:
+                covers += [[terms[z]] + terms[:z] + terms[z + 1:] for z, t in enumerate(terms) if t[2] == 0]
+    return (best[0], covers) if covers else None
+
+
+def mux_assign(table, phases=MUX_PHASES):
+    """[(phase, cost, covers)] per orientation: the phase with its cheapest cover; ties go
+    to fewer terms, then to the earlier phase."""
+    out = []
+    for _pid, _o, cells, _h, _w in table:
+        cands = []
+        for pi, ph in enumerate(phases):
+            cov = mux_covers(cells, ph)
+            if cov is not None:
+                cands.append((cov[0], len(cov[1][0]), pi, ph, cov[1]))
+        cost, _nt, _pi, ph, covers = min(cands)
+        out.append((ph, cost, covers))
+    return out
+
+
+def mux_classes(table, phases=MUX_PHASES):
+    """{phase: [(height, ((d, kind, zero), ...), entries)]}, entries as in zero_classes.
+    A class is keyed by its zero pattern too, so every column-0 term is flagged.  Where an
+    orientation has several covers of its cheapest cost, the one that shares a class with
+    the most others is taken (greedily, the largest class first): fewer classes, less code."""
+    assign = mux_assign(table, phases)
+    out = {}
+    for ph in phases:
+        cands = {}  # class key -> {g: columns}
+        for g, ((_pid, _o, _cells, h, _w), (aph, _cost, covers)) in enumerate(zip(table, assign)):
+            if aph != ph:
+                continue
+            for terms in covers:
+                key = (h, tuple((d, k, int(j > 0 and c == 0)) for j, (k, d, c) in enumerate(terms)))
+                cands.setdefault(key, {}).setdefault(g, tuple(c for _k, _d, c in terms))
+        classes, left = {}, {g for m in cands.values() for g in m}
+        while left:
+            key = min(cands, key=lambda k: (-len(left & set(cands[k])), k))
+            classes[key] = [(g, table[g][0], cands[key][g]) for g in sorted(left & set(cands[key]))]
+            left -= set(cands[key])
+        order = sorted(classes, key=lambda k: (k[0], len(k[1]), tuple(d * 4 + kd for d, kd, _z in k[1]),
+                                               tuple(z for _d, _kd, z in k[1])))
+        out[ph] = [(h, terms, classes[(h, terms)]) for h, terms in order]
+    return out
+
+
+def mux_stats(table, phases=MUX_PHASES):
+    """Per phase: (phase, orientations, plain classes, classes, weighted NT, weighted nz);
+    the weight is the anchor rows 21 - h."""
+    rows = []
+    for ph, cls in mux_classes(table, phases).items():
+        nt = sum((21 - h) * len(t) * len(e) for h, t, e in cls)
+        nz = sum((21 - h) * sum(1 for c in cols if c) for h, _t, e in cls for _g, _pid, cols in e)
+        plain = {(h, tuple(x[:2] for x in t)) for h, t, _e in cls}
+        rows.append((ph, sum(len(e) for _h, _t, e in cls), len(plain), len(cls), nt, nz))
+    return rows
+
+
+def render_mux(table):
+    """The per-phase lists of -DBK_STENCIL_MUX: BK_CLASS_LIST_MUX_P / _T / _U / _Q in the token
+    format of the lists above (kind 1 = the second plane of the phase), indexing a table
+    of their own (the term columns differ), phase after phase."""
+    cls = mux_classes(table)
+    lines = [f"#define BK_NUM_CLASSES_MUX {sum(len(c) for c in cls.values())}"]
+    i = 0
+    for ph in MUX_PHASES:
+        lines.append(f"#define BK_CLASS_LIST_MUX_{ph.upper()}(X) \\")
+        for h, terms, ents in cls[ph]:
+            toks = ", ".join(str(d * 8 + 4 * z + kd) for d, kd, z in terms)
+            lines.append(f"    X({i}, {i + len(ents)}, {h}, {toks}) \\")
+            i += len(ents)
+        lines.append("")
+    lines.append("#define BK_CLASS_TABLE_MUX_INIT { \\")
+    for ph in MUX_PHASES:
+        for _h, _t, ents in cls[ph]:
+            for g, pid, cols in ents:
+                w1 = sum(c << (3 * (j - 1)) for j, c in enumerate(cols) if j > 0)
+                lines.append(f"    {{{hex(pid | (g << 8))}, {hex(w1)}}}, \\")
+    lines.append("}")
+    return lines
+
+
 def zero_stats(table):
     """Per plain class: anchor-row-weighted shifts, zero shifts, and the zero shifts a
     'common' flagging removes (a sweep's ranking)."""
@@ -280,6 +405,7 @@ def render(table):
         lines.append("    {" + ", ".join(words) + "}, \\")
     lines.append("}")
     lines += render_classes(table)
+    lines += render_mux(table)
     lines += render_cell_hash()
     return "\n".join(lines) + "\n"
 
@@ -293,6 +419,17 @@ def main():
             print(f"{ci:5d} {h:2d} {nt:6d} {ne:7d} {sh:7d} {z:5d} {cm:7d}  {mode}")
             tot = [tot[0] + sh, tot[1] + z, tot[2] + cm]
         print("total", *tot)
+        return
+    if "--mux-stats" in sys.argv:
+        table = orientations()
+        for phases in (("p",), ("p", "t"), ("p", "t", "u"), ("p", "t", "u", "q")):
+            print("phases", " ".join(phases))
+            print("  phase orients plain classes    NT    nz")
+            tot = [0, 0]
+            for ph, no, npl, nc, nt, nz in mux_stats(table, phases):
+                print(f"  {ph:>5} {no:7d} {npl:5d} {nc:7d} {nt:5d} {nz:5d}")
+                tot = [tot[0] + nt, tot[1] + nz]
+            print(f"  total NT {tot[0]} nz {tot[1]} NT+nz {sum(tot)}")
         return
     out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
                        "reinforcementlearning_blokus_amd", "csrc", "orient_table.h")
