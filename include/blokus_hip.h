@@ -707,6 +707,65 @@ int bk_winprob_eval(bk_handle h, const bk_state* states, const bk_fset* sets, in
                     const int32_t* turn_index, int32_t max_turns, const bk_winprob_model* model,
                     double* prob, double* pair_logit, uint8_t* status, int mem);
 
+/*
+ * bk_step_metrics -- the integers behind one line of the strategy step log
+ * (analytics/logging/logger.py StrategyLogger.on_step with analytics/metrics/ *) for n
+ * (before, move, after) steps in one launch (added within ABI 7: new symbols only).
+ * before[i] / sets_before[i] is the board the move was made on, after[i] / sets_after[i] the
+ * board it left; "frontier" means the keys of the tables, as bk_snapshot_features reads them
+ * (slots 0..mask, keys 0..399, stale keys included).  The placed cells come from the
+ * orientation table at the anchor (Move.get_positions), not from a difference of the boards.
+ * Every float of a StepLog line is one division of two of these integers, done on the host.
+ *
+ * bk_step is a record of its own: none of the packed move encodings (g * 400 + 20 r + c of
+ * bk_mcts / bk_arena_step) carries the mover, and the log's action is (piece_id, orientation).
+ */
+typedef struct bk_step {             /* POD, 8 bytes */
+    uint8_t mover;                   /* 0..3 = Player.value - 1                                    */
+    uint8_t piece_id;                /* 1..21                                                      */
+    uint8_t orientation;             /* Move.orientation: index into the piece's orientation list  */
+    uint8_t anchor_row, anchor_col;  /* Move.anchor_row / anchor_col (top-left of the bounding box)*/
+    uint8_t reserved[3];             /* 0                                                          */
+} bk_step;
+
+#define BK_STEP_ST_TABLE 1u /* BK_SNAP_ST_TABLE's conditions on either board's tables              */
+#define BK_STEP_ST_STATE 2u /* BK_SNAP_ST_STATE's conditions on either board                       */
+#define BK_STEP_ST_MOVE  4u /* the step does not describe the pair of boards: a mover above 3, a
+                               piece or orientation outside the table, a placed cell off the board
+                               or on a cell occupied in `before`, a piece already used in `before`,
+                               or an `after` whose planes and used masks are not `before` plus
+                               exactly this piece for this mover.  The fields are still written
+                               (mover taken mod 4; no placed cells for a piece outside the table;
+                               off-board cells skipped by dist_to_opp_min) */
+typedef struct bk_step_rec {         /* one per step; POD, 64 bytes, no padding */
+    uint32_t moves_before[4];        /*  0: len(get_legal_moves(state, p)), players 0..3 (mobility.py:20-44) */
+    uint32_t moves_after[4];         /* 16: the same on next_state                                        */
+    uint16_t frontier_before[4];     /* 32: len(state.get_frontier(p)) = the table's active keys (corners.py) */
+    uint16_t frontier_after[4];      /* 40: the same on next_state                                        */
+    uint16_t area_before;            /* 48: np.sum(state.grid == mover) (territory.py:27-33)              */
+    uint16_t area_after;             /* 50: the same on next_state                                        */
+    uint16_t perimeter_before;       /* 52: calculate_perimeter of the mover's mask (territory.py:35-57)  */
+    uint16_t perimeter_after;        /* 54                                                                */
+    uint16_t bbox_area_after;        /* 56: bounding box of the mover's cells after the move, 0 if none   */
+    uint16_t center_dist_sum;        /* 58: sum over the placed cells of |r - 9.5| + |c - 9.5| (center.py:23) */
+    uint8_t  center_gain;            /* 60: placed cells with that distance <= 4                          */
+    uint8_t  placed_cells;           /* 61: len(placed_squares)                                           */
+    uint8_t  dist_to_opp_min;        /* 62: min Manhattan distance from a placed cell to an opponent cell
+                                            of the before grid; 40 when there is none (proximity.py)      */
+    uint8_t  status;                 /* 63: 0 or BK_STEP_ST_* bits; never silently wrong                  */
+} bk_step_rec;
+
+/* Both BK_MEM_HOST (staged through the handle's launch plan and arena) and BK_MEM_DEVICE
+   (device pointers: sets 16-byte, states, steps and out 8-byte aligned, else BK_EINVAL).
+   BK_EINVAL, before any GPU work, for a null pointer or n < 0; n == 0 is BK_OK without a
+   launch; launched on the handle's current stream, one block per step, timed for
+   bk_last_kernel_ms ("k_steplog"). */
+int bk_step_metrics(bk_handle h, const bk_state* before, const bk_fset* sets_before,
+                    const bk_state* after, const bk_fset* sets_after, const bk_step* steps, int32_t n,
+                    bk_step_rec* out /* n */, int mem);
+/* sizeof(bk_step_rec) as the library was compiled (binding checks; no GPU call). */
+int bk_step_rec_size(void);
+
 /* Average duration (ms) of the most recent bk_rollout/bk_movegen kernel on the handle
    stream, measured with HIP events around that launch. */
 int bk_last_kernel_ms(bk_handle h, float* ms);

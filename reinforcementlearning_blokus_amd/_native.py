@@ -39,6 +39,7 @@ EXPORTS = (
     "bk_telemetry", "bk_telemetry_set_tables", "bk_debug_telemetry_mt",
     "bk_snapshot_features", "bk_snapshot_rec_size",
     "bk_winprob_eval", "bk_winprob_model_size",
+    "bk_step_metrics", "bk_step_rec_size",
 )
 # bk_debug_mcts_failure record (include/blokus_hip.h BK_DIAG_*)
 DIAG_WORDS = 64
@@ -160,6 +161,22 @@ class BkWinprobModel(C.Structure):
 assert C.sizeof(BkWinprobModel) == 8 * (3 * SNAPSHOT_COLUMNS + 1)
 
 
+STEP_ST_TABLE, STEP_ST_STATE, STEP_ST_MOVE = 1, 2, 4  # bk_step_rec.status bits
+# bk_step: one logged move (mover 0..3, the reference's Move fields)
+STEP_DTYPE = np.dtype([("mover", "u1"), ("piece_id", "u1"), ("orientation", "u1"), ("anchor_row", "u1"),
+                       ("anchor_col", "u1"), ("reserved", "u1", (3,))])
+# bk_step_rec: the integers behind one StepLog line
+STEP_REC_DTYPE = np.dtype({
+    "names": ["moves_before", "moves_after", "frontier_before", "frontier_after", "area_before", "area_after",
+              "perimeter_before", "perimeter_after", "bbox_area_after", "center_dist_sum", "center_gain",
+              "placed_cells", "dist_to_opp_min", "status"],
+    "formats": [("<u4", (4,)), ("<u4", (4,)), ("<u2", (4,)), ("<u2", (4,)), "<u2", "<u2", "<u2", "<u2", "<u2", "<u2",
+                "u1", "u1", "u1", "u1"],
+    "offsets": [0, 16, 32, 40, 48, 50, 52, 54, 56, 58, 60, 61, 62, 63],
+    "itemsize": 64})
+assert STEP_DTYPE.itemsize == 8 and STEP_REC_DTYPE.itemsize == 64
+
+
 class BkMctsCfg(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("max_rollout_moves", C.c_int32), ("exploration", C.c_double),
                 ("use_tt", C.c_int32), ("node_cap", C.c_int32), ("tt_cap", C.c_int32),
@@ -274,10 +291,15 @@ def load():
             "bk_winprob_eval": (C.c_int, [vp, vp, vp, C.c_int32, vp, C.c_int32, P(BkWinprobModel), vp, vp, vp,
                                           C.c_int]),
             "bk_winprob_model_size": (C.c_int, []),
+            "bk_step_metrics": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_int]),
+            "bk_step_rec_size": (C.c_int, []),
         }
         for name, (res, args) in sigs.items():
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
+        if L.bk_step_rec_size() != STEP_REC_DTYPE.itemsize:
+            raise NativeUnavailable(f"{LIB_PATH}: bk_step_rec is {L.bk_step_rec_size()} bytes, STEP_REC_DTYPE "
+                                    f"{STEP_REC_DTYPE.itemsize}: rebuild it (__graft_entry__.build())")
         _lib = L
         return L
 
@@ -637,6 +659,13 @@ class Handle:
                                          C.c_void_p(prob_ptr or 0), C.c_void_p(logit_ptr or 0),
                                          C.c_void_p(status_ptr or 0), mem)
         self.check(rc, "bk_winprob_eval")
+
+    def step_metrics(self, before_ptr, sets_before_ptr, after_ptr, sets_after_ptr, steps_ptr, n, out_ptr, mem):
+        with self._lock:
+            rc = self._L.bk_step_metrics(self._h, C.c_void_p(before_ptr or 0), C.c_void_p(sets_before_ptr or 0),
+                                         C.c_void_p(after_ptr or 0), C.c_void_p(sets_after_ptr or 0),
+                                         C.c_void_p(steps_ptr or 0), n, C.c_void_p(out_ptr or 0), mem)
+        self.check(rc, "bk_step_metrics")
 
     def advance(self, roots_ptr, n_roots, index_ptr, n, cfg: BkRolloutCfg, seeds_ptr, out_ptr, mem):
         with self._lock:

@@ -9,6 +9,7 @@
 //   engine/telemetry.py:17-198        collect_all_player_metrics (bk_telemetry)
 //   analytics/winprob/features.py:106-192 snapshot feature rows (bk_snapshot_features)
 //   mcts/learned_evaluator.py:95-144  pairwise_logreg win probabilities (bk_winprob_eval)
+//   analytics/logging/logger.py:49-148 + analytics/metrics/* step-log integers (bk_step_metrics)
 //
 // Design (DESIGN.md has the full story):
 //   * one lane = one board (one game); 64 games per wave, all control flow uniform
@@ -69,6 +70,7 @@
 #define BK_U_COOP_H 11
 #define BK_U_TELEMETRY 12
 #define BK_U_SNAPSHOT 13
+#define BK_U_STEPLOG 14
 #ifndef BK_TU
 #define BK_TU 0
 #endif
@@ -6378,6 +6380,239 @@ __global__ void k_snapshot(SnapArgs a);
 __global__ void k_winprob(WinprobArgs a);
 #endif
 
+// ------------------------------------------------------------------------------------
+// Step log: the integers behind analytics/logging/logger.py StrategyLogger.on_step with
+// analytics/metrics/* for batches of (before, move, after) steps (bk_step_metrics).  One
+// block of eight waves per step: wave w counts the legal moves of player w & 3 on the
+// before (w < 4) or after (w >= 4) board as k_snapshot's phase A does (derive_rows /
+// coop_live_orients / coop_ok_counts / coop_scan, counts only: no per-piece sums, flood
+// fill, doubles or tables) and the active keys of that player's frontier table.  Wave 0
+// also runs the mover's scans of the before board, the placed cells and the checks of the
+// step against the two boards, wave 4 the mover's scans of the after board, with board row
+// R in lane R.  After the block barrier wave 0 assembles the record and copies it out.
+// ------------------------------------------------------------------------------------
+#define STEP_WAVES 8
+struct StepArgs {
+    const bk_state* before;
+    const bk_fset* sets_before;
+    const bk_state* after;
+    const bk_fset* sets_after;
+    const bk_step* steps;
+    int32_t n;
+    bk_step_rec* out;
+};
+
+static_assert(sizeof(bk_step) == 8, "steps are read as one 8-byte record");
+static_assert(sizeof(bk_step_rec) == 64 && sizeof(bk_step_rec) % 8 == 0, "the record is copied out as dwords");
+static_assert(BK_STEP_ST_TABLE == BK_SNAP_ST_TABLE && BK_STEP_ST_STATE == BK_SNAP_ST_STATE, "shared status bits");
+
+#if BK_DEF(BK_U_STEPLOG)
+// each piece's first global orientation and its number of orientations, from the orientation table
+struct StepTab {
+    uint8_t first[BK_PIECES], orients[BK_PIECES];
+};
+constexpr uint32_t kStepInfo[BK_NUM_ORIENTS] = BK_ORIENT_INFO_INIT;
+constexpr StepTab step_tab() {
+    StepTab t{};
+    for (int g = BK_NUM_ORIENTS - 1; g >= 0; --g) {
+        const int i = (int)(kStepInfo[g] & 0xFFu) - 1;
+        t.first[i] = (uint8_t)g;
+        t.orients[i] = (uint8_t)(t.orients[i] + 1);
+    }
+    return t;
+}
+__constant__ StepTab kStepTab = step_tab();
+
+__device__ __forceinline__ uint32_t step_wave_or(uint32_t v) {
+#pragma unroll
+    for (int o = WAVE / 2; o; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+
+// calculate_perimeter of a mask held one row per lane (lanes >= 20 hold 0): the 0/1
+// transitions of the mask padded by one cell, along both axes
+__device__ __forceinline__ uint32_t step_perimeter(uint32_t m, int lane) {
+    const uint32_t up = __shfl_up(m, 1);
+    const uint32_t horiz = (m ^ (m << 1)) & 0x1FFFFFu;   // columns -1|0 .. 19|20 of this row
+    const uint32_t vert = m ^ (lane >= 1 ? up : 0u);     // rows lane-1|lane: lanes 0..20 (lane 20 holds 0)
+    return tel_wave_sum((uint32_t)__builtin_popcount(horiz) + (uint32_t)__builtin_popcount(vert), lane);
+}
+
+__global__ __launch_bounds__(STEP_WAVES * WAVE) void k_steplog(StepArgs a) {
+    __shared__ __attribute__((aligned(16))) uint2 s_rows[20 * WAVE];  // column w: wave w's {B, C} rows
+    __shared__ uint32_t s_own[2][4][20], s_occ[2][20];
+    __shared__ uint32_t s_mob[STEP_WAVES], s_fsz[STEP_WAVES], s_status;
+    __shared__ int16_t s_otab[STEP_WAVES][2 * WAVE];
+    __shared__ __attribute__((aligned(8))) bk_step_rec s_rec;
+    constexpr int REC_WORDS = (int)(sizeof(bk_step_rec) / 4);
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const int side = w >> 2, p = w & 3;
+    const size_t step = blockIdx.x;  // the grid is exactly n blocks
+    const bk_state* sb = a.before + step;
+    const bk_state* sa = a.after + step;
+    const bk_state* s = side ? sa : sb;
+    const bk_fset* fs = (side ? a.sets_after : a.sets_before) + step;
+
+    for (int i = tid; i < 2 * 4 * 20; i += STEP_WAVES * WAVE) {
+        const bk_state* t = i < 80 ? sb : sa;
+        const int j = i < 80 ? i : i - 80;
+        (&s_own[0][0][0])[i] = plane_row(t->planes[j / 20], j % 20);
+    }
+    if (tid < REC_WORDS) reinterpret_cast<bk_u32_alias*>(&s_rec)[tid] = 0u;
+    if (tid == 0) s_status = 0u;
+    __syncthreads();
+    if (tid < 2 * 20) {
+        const int sd = tid / 20, R = tid - 20 * sd;
+        const uint32_t o0 = s_own[sd][0][R], o1 = s_own[sd][1][R], o2 = s_own[sd][2][R], o3 = s_own[sd][3][R];
+        s_occ[sd][R] = o0 | o1 | o2 | o3;
+        if ((o0 & (o1 | o2 | o3)) | (o1 & (o2 | o3)) | (o2 & o3)) atomicOr(&s_status, BK_STEP_ST_STATE);
+    }
+    if (lane == 0 && ((s->planes[p][BK_MASK_WORDS - 1] >> (BK_CELLS - 64 * (BK_MASK_WORDS - 1))) || (s->used[p] >> BK_PIECES)))
+        atomicOr(&s_status, BK_STEP_ST_STATE);
+    // the player's frontier size: the table's active keys, read as snap_rows reads them
+    {
+        int tmask = (int)fs->mask[p];
+        bool bad_table = tmask >= BK_FSET_SLOTS;
+        tmask = tmask < BK_FSET_SLOTS ? tmask : BK_FSET_SLOTS - 1;
+        uint32_t fsize = 0;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int sl = lane + WAVE * h;
+            const int k = sl <= tmask ? (int)fs->key[p][sl] : -1;
+            bad_table = bad_table || k >= BK_CELLS || k < -2;  // (-1 unused, -2 dummy)
+            fsize += (uint32_t)__popcll(__ballot(k >= 0 && k < BK_CELLS));
+        }
+        if (__ballot(bad_table) && lane == 0) atomicOr(&s_status, BK_STEP_ST_TABLE);
+        if (lane == 0) s_fsz[w] = fsize;
+    }
+    __syncthreads();  // the occupancy rows are complete
+
+    // ---- the legal-move count of player p on this wave's board
+    {
+        const bool first = (s->first_move >> p) & 1u;
+        uint2* rows = s_rows + w;
+        {
+            uint32_t own[20], occ[20], B[20], C[20];
+#pragma unroll
+            for (int R = 0; R < 20; ++R) { own[R] = s_own[side][p][R]; occ[R] = s_occ[side][R]; }
+            derive_rows(own, occ, first, p, B, C);
+#pragma unroll
+            for (int R = 0; R < 20; ++R) rows[R * WAVE] = make_uint2(B[R], C[R]);
+        }
+        tel_wave_sync();
+        int og[2];
+        const uint32_t nlive = coop_live_orients(~s->used[p] & 0x1FFFFFu, lane, s_otab[w], og);
+        uint32_t ok0[20], ok1[20], cnt[2];
+        coop_ok_counts(rows, og, nlive, ok0, ok1, cnt);
+        const uint32_t mob = coop_scan(cnt, lane).total;
+        if (lane == 0) s_mob[w] = mob;
+    }
+
+    // ---- the mover's scans, row R in lane R (the other lanes hold empty rows): wave 0 the
+    // before board, the placed cells and the checks, wave 4 the after board
+    if (p == 0) {
+        const bk_step sp = a.steps[step];
+        const int m = sp.mover & 3;
+        const bool rl = lane < 20;
+        const int R = rl ? lane : 0;
+        const uint32_t r_own = rl ? s_own[side][m][R] : 0u;
+        const uint32_t area = tel_wave_sum((uint32_t)__builtin_popcount(r_own), lane);
+        const uint32_t perim = step_perimeter(r_own, lane);
+        if (side == 1) {
+            // calculate_bbox_area: rows from the non-empty lanes, columns from the OR of the rows
+            const uint64_t rb = __ballot(r_own != 0u);
+            const uint32_t cols = step_wave_or(r_own);
+            uint32_t bbox = 0;
+            if (rb) {
+                const uint32_t hgt = (uint32_t)(63 - __clzll((unsigned long long)rb)) - (uint32_t)(__ffsll((unsigned long long)rb) - 1) + 1u;
+                const uint32_t wid = (31u - (uint32_t)__builtin_clz(cols)) - (uint32_t)__builtin_ctz(cols) + 1u;
+                bbox = hgt * wid;
+            }
+            if (lane == 0) {
+                s_rec.area_after = (uint16_t)area;
+                s_rec.perimeter_after = (uint16_t)perim;
+                s_rec.bbox_area_after = (uint16_t)bbox;
+            }
+        } else {
+            const int pi = (int)sp.piece_id - 1;
+            bool bad = sp.mover > 3;
+            const bool piece_ok = pi >= 0 && pi < BK_PIECES && sp.orientation < kStepTab.orients[pi < 0 || pi >= BK_PIECES ? 0 : pi];
+            bad = bad || !piece_ok;
+            const int g = piece_ok ? (int)kStepTab.first[pi] + (int)sp.orientation : 0;
+            const int n = piece_ok ? (int)((kInfo[g] >> 8) & 0xFFu) : 0;
+            if (piece_ok && ((sb->used[m] >> pi) & 1u)) bad = true;  // a piece already used
+            const uint32_t r_opp = rl ? (s_occ[0][R] & ~r_own) : 0u;
+            uint32_t pm = 0, csum2 = 0, gain = 0, dmin = 40;
+#pragma unroll
+            for (int q = 0; q < 5; ++q) {
+                if (q >= n) continue;  // (uniform)
+                const uint32_t cell = kCells[g][q];
+                const int r = (int)sp.anchor_row + (int)(cell >> 8), c = (int)sp.anchor_col + (int)(cell & 0xFFu);
+                // |r - 9.5| + |c - 9.5|, doubled: two odd numbers, so every term is an integer
+                const int d2 = (2 * r - 19 < 0 ? 19 - 2 * r : 2 * r - 19) + (2 * c - 19 < 0 ? 19 - 2 * c : 2 * c - 19);
+                csum2 += (uint32_t)d2;
+                gain += d2 <= 8 ? 1u : 0u;
+                if (r > 19 || c > 19) { bad = true; continue; }  // (uniform) off the board
+                if ((s_occ[0][r] >> c) & 1u) bad = true;          // on an occupied cell
+                pm |= lane == r ? (1u << c) : 0u;
+                // the nearest opponent cell of this lane's row to column c: the highest set bit at
+                // or below c, the lowest above it
+                uint32_t d = 40;
+                if (r_opp) {
+                    const uint32_t at_or_below = (2u << c) - 1u;
+                    const uint32_t lo = r_opp & at_or_below, hi = r_opp & ~at_or_below;
+                    uint32_t dc = 40;
+                    if (lo) dc = (uint32_t)c - (31u - (uint32_t)__builtin_clz(lo));
+                    if (hi) { const uint32_t t = (uint32_t)__builtin_ctz(hi) - (uint32_t)c; dc = t < dc ? t : dc; }
+                    d = (uint32_t)(R < r ? r - R : R - r) + dc;
+                }
+                dmin = d < dmin ? d : dmin;
+            }
+#pragma unroll
+            for (int o = WAVE / 2; o; o >>= 1) {
+                const uint32_t t = (uint32_t)__shfl_xor((int)dmin, o);
+                dmin = t < dmin ? t : dmin;
+            }
+            // after = before plus exactly this piece for this mover: planes and used masks
+            bool differs = false;
+            if (rl) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) differs = differs || s_own[1][q][R] != (s_own[0][q][R] | (q == m ? pm : 0u));
+            }
+            if (lane < 4)
+                differs = differs || (sa->used[lane] & 0x1FFFFFu) !=
+                                         ((sb->used[lane] & 0x1FFFFFu) | (lane == m && piece_ok ? 1u << pi : 0u));
+            if (__ballot(differs)) bad = true;
+            if (lane == 0) {
+                s_rec.area_before = (uint16_t)area;
+                s_rec.perimeter_before = (uint16_t)perim;
+                s_rec.center_dist_sum = (uint16_t)(csum2 >> 1);
+                s_rec.center_gain = (uint8_t)gain;
+                s_rec.placed_cells = (uint8_t)n;
+                s_rec.dist_to_opp_min = (uint8_t)dmin;
+                if (bad) atomicOr(&s_status, BK_STEP_ST_MOVE);
+            }
+        }
+    }
+    __syncthreads();  // the eight counts, the scans and the status are complete
+    if (w == 0) {
+        if (lane < 4) {
+            s_rec.moves_before[lane] = s_mob[lane];
+            s_rec.moves_after[lane] = s_mob[4 + lane];
+            s_rec.frontier_before[lane] = (uint16_t)s_fsz[lane];
+            s_rec.frontier_after[lane] = (uint16_t)s_fsz[4 + lane];
+        }
+        if (lane == 0) s_rec.status = (uint8_t)s_status;
+        tel_wave_sync();
+        bk_u32_alias* dst = reinterpret_cast<bk_u32_alias*>(a.out + step);
+        if (lane < REC_WORDS) dst[lane] = reinterpret_cast<const bk_u32_alias*>(&s_rec)[lane];
+    }
+}
+#else
+__global__ void k_steplog(StepArgs a);
+#endif
+
 #if BK_DEF(BK_U_HOST)
 // ------------------------------------------------------------------------------------
 // C ABI
@@ -7194,6 +7429,32 @@ int bk_snapshot_features(bk_handle h, const bk_state* states, const bk_fset* set
     if (int rc = st.commit()) return rc;
     SnapArgs a{s_states.dev(), s_sets.dev(), s_turn.dev(), n, max_turns, s_rec.dev(), s_feat.dev()};
     BK_LAUNCH(h, k_snapshot, dim3(n), dim3(SNAP_WAVES * WAVE), a);
+    return st.finish();
+}
+
+int bk_step_rec_size(void) { return (int)sizeof(bk_step_rec); }
+
+int bk_step_metrics(bk_handle h, const bk_state* before, const bk_fset* sets_before, const bk_state* after,
+                    const bk_fset* sets_after, const bk_step* steps, int32_t n, bk_step_rec* out, int mem) {
+    if (!h || !before || !sets_before || !after || !sets_after || !steps || !out || n < 0 ||
+        (mem != BK_MEM_HOST && mem != BK_MEM_DEVICE))
+        return set_err(h, BK_EINVAL, "bk_step_metrics: invalid arguments%s", "");
+    if (mem == BK_MEM_DEVICE && (((uintptr_t)sets_before & 15) || ((uintptr_t)sets_after & 15) || ((uintptr_t)before & 7) ||
+                                 ((uintptr_t)after & 7) || ((uintptr_t)steps & 7) || ((uintptr_t)out & 7)))
+        return set_err(h, BK_EINVAL, "bk_step_metrics: sets must be 16-byte, states, steps and out 8-byte aligned%s", "");
+    if (n == 0) return BK_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    BK_IDLE(h, "bk_step_metrics");
+    Staging st(h, mem);
+    const auto s_before = st.in(before, sizeof(bk_state) * (size_t)n);
+    const auto s_sets_before = st.in(sets_before, sizeof(bk_fset) * (size_t)n);
+    const auto s_after = st.in(after, sizeof(bk_state) * (size_t)n);
+    const auto s_sets_after = st.in(sets_after, sizeof(bk_fset) * (size_t)n);
+    const auto s_steps = st.in(steps, sizeof(bk_step) * (size_t)n);
+    const auto s_out = st.out(out, sizeof(bk_step_rec) * (size_t)n);
+    if (int rc = st.commit()) return rc;
+    StepArgs a{s_before.dev(), s_sets_before.dev(), s_after.dev(), s_sets_after.dev(), s_steps.dev(), n, s_out.dev()};
+    BK_LAUNCH(h, k_steplog, dim3(n), dim3(STEP_WAVES * WAVE), a);
     return st.finish();
 }
 

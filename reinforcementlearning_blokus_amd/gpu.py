@@ -266,6 +266,43 @@ class BlokusGPU:
                                  N.MEM_HOST)
         return prob, logit, status
 
+    def step_metrics(self, before, sets_before, after, sets_after, steps):
+        """The integers behind n strategy-log steps in one launch (bk_step_metrics, k_steplog):
+        before / after the packed boards around each move and sets_before / sets_after their
+        frontier tables (as telemetry: numpy records or uint8 rows, host or torch cuda), steps
+        N.STEP_DTYPE[n] (uint8[n, 8]).  Returns N.STEP_REC_DTYPE[n] (torch in: a uint8 cuda
+        tensor [n, 64]); analytics.metrics.metrics_from_step_record turns one into the 28
+        metrics.  Check ``status`` before trusting a record."""
+        item, fitem, sitem = N.STEP_REC_DTYPE.itemsize, N.FSET_DTYPE.itemsize, N.STEP_DTYPE.itemsize
+        if _is_torch(before):
+            import torch
+            n = before.shape[0]
+            for t, name, width in ((before, "before", 256), (sets_before, "sets_before", fitem), (after, "after", 256),
+                                   (sets_after, "sets_after", fitem), (steps, "steps", sitem)):
+                _check_device_tensor(t, name, torch.uint8, (n, width), self.device)
+            out = torch.empty((n, item), dtype=torch.uint8, device=before.device)
+            self._stream_from_torch()
+            self.handle.step_metrics(before.data_ptr(), sets_before.data_ptr(), after.data_ptr(), sets_after.data_ptr(),
+                                     steps.data_ptr(), n, out.data_ptr(), N.MEM_DEVICE)
+            return out
+        sp = np.ascontiguousarray(steps).view(np.uint8)
+        if sp.size % sitem:
+            raise ValueError(f"steps: {sp.size} bytes are no whole number of {sitem}-byte bk_step records")
+        n = sp.size // sitem
+        sp = sp.reshape(n, sitem)
+        bufs = []
+        for x, name, width in ((before, "before", 256), (sets_before, "sets_before", fitem), (after, "after", 256),
+                               (sets_after, "sets_after", fitem)):
+            a = np.ascontiguousarray(x).view(np.uint8)
+            if a.size != n * width:
+                raise ValueError(f"{name}: {a.size} bytes for {n} steps of {width}")
+            bufs.append(a.reshape(n, width))
+        out = np.zeros(n, dtype=N.STEP_REC_DTYPE)
+        self.handle.set_stream(None)
+        self.handle.step_metrics(bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data, bufs[3].ctypes.data,
+                                 sp.ctypes.data, n, out.ctypes.data, N.MEM_HOST)
+        return out
+
     def has_moves(self, states):
         """uint8 mask per state: bit p set iff player p has a legal move (move_generator.py:961)."""
         if _is_torch(states):
