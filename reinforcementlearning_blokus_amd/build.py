@@ -19,7 +19,8 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found")
 
 
-DEPS = [SRC, os.path.join(_HERE, "csrc", "orient_table.h"), os.path.join(ROOT, "include", "blokus_hip.h")]
+DEPS = [SRC, os.path.join(_HERE, "csrc", "orient_table.h"), os.path.join(_HERE, "csrc", "exp_cr.h"),
+        os.path.join(ROOT, "include", "blokus_hip.h")]
 HASH_FILE = OUT + ".srchash"  # sha256 of the sources the .so was built from
 
 

@@ -3217,6 +3217,12 @@ __device__ __forceinline__ double draw_double(const RolloutArgs& a, Game& g, con
 __device__ __forceinline__ void stop_info(const RolloutArgs& a, const Game& g, const Planes& P, uint32_t* my, int lane,
                                        uint2* rows_lds, const bk_fset* fs, int fmask, int p, uint32_t avail,
                                        uint32_t total) {
+// The reward is written with the operators themselves, under this pragma: __dmul_rn /
+// __dadd_rn are plain * and + compiled in their header's context, so they stay open to
+// contraction wherever they are inlined, and a * b + c * d became fma(c, d, a * b), one
+// rounding fewer than CPython makes (piece 21 at distance 9.0: 0x1.5333333333333p+1
+// instead of 0x1.5333333333334p+1)
+#pragma clang fp contract(off)
     bk_stop_info si;
     si.n_legal = (int32_t)total;
     si.quick_index = 0;
@@ -3257,8 +3263,8 @@ __device__ __forceinline__ void stop_info(const RolloutArgs& a, const Game& g, c
         }
         if (q >= 0) {
             si.quick_index = (int32_t)k3[q];
-            si.quick_reward = __dadd_rn(__dmul_rn((double)(kInfo[g3[q]] & 0xFFu), 0.1),
-                                        __dmul_rn(__dadd_rn(20.0, -best), 0.05));
+            const double size_term = (double)(kInfo[g3[q]] & 0xFFu) * 0.1, centre_term = (20.0 - best) * 0.05;
+            si.quick_reward = size_term + centre_term;
         }
     }
     a.stop_out[g.pid] = si;
@@ -6341,7 +6347,11 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
 // u_k = ((f[p][k] - f[q][k]) - mean[k]) / scale[k] * coef[k] for the three q and leaves them
 // in LDS; lane j < 3 adds opponent j's 34 terms in ascending k, then the intercept, and takes
 // s = 1 / (1 + exp(-t)); lane 0 averages the three.  One rounding per operation, no FMA.
-// exp overflows to +inf (s = 0) and underflows to 0 (s = 1) for very large |t|.
+// exp is bk_exp_cr (exp_cr.h): rounded from a double-double value, so it is the correctly
+// rounded exp wherever a host libm's is; the device library's (within 1 ulp) left 1 prob of
+// 172 on the edge boards 2 ulp from CPython's.  It overflows to +inf (s = 0) and underflows
+// to 0 (s = 1) for very large |t|.
+#include "exp_cr.h"
 __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_winprob(WinprobArgs a) {
 #pragma clang fp contract(off)
     __shared__ __attribute__((aligned(8))) double s_feat[SNAP_WAVES][BK_SNAPSHOT_COLUMNS];
@@ -6368,7 +6378,7 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_winprob(WinprobArgs a) {
 #pragma unroll 1
         for (int k = 0; k < BK_SNAPSHOT_COLUMNS; ++k) t = __dadd_rn(t, s_u[p][lane][k]);
         t = __dadd_rn(t, a.m.intercept);
-        sg = __ddiv_rn(1.0, __dadd_rn(1.0, exp(-t)));
+        sg = __ddiv_rn(1.0, __dadd_rn(1.0, bk_exp_cr(-t)));
         if (a.pair_logit != nullptr) a.pair_logit[(board * 4 + (size_t)p) * 3 + (size_t)lane] = t;
     }
     const double s1 = __shfl(sg, 1), s2 = __shfl(sg, 2);

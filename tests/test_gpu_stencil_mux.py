@@ -25,12 +25,12 @@ import pytest
 from oracle import pyoracle as O
 from reinforcementlearning_blokus_amd import _native as N
 from tests import rules_reference as R
+from tests.edge_boards import strip_states
 from tests.helpers import oracle_fset, oracle_states, pack_many
 
 pytestmark = pytest.mark.gpu
 
 SEED = 20260412
-STRIP = 3
 LANES = 64
 FIELDS = ("planes", "used", "first_move", "current_player", "move_count")
 
@@ -46,39 +46,12 @@ def _pool_map(fn, items):
         return list(ex.map(fn, items))
 
 
-def strip_states():
-    """Opponents own every cell but a STRIP-wide band along one edge; player 0 owns one
-    cell just outside the band, so the band holds two of its corner cells."""
-    out = []
-    for edge in ("left", "right", "top", "bottom"):
-        free = np.zeros((R.SIZE, R.SIZE), dtype=bool)
-        if edge == "left":
-            free[:, :STRIP] = True
-            own = (10, STRIP)
-        elif edge == "right":
-            free[:, R.SIZE - STRIP:] = True
-            own = (10, R.SIZE - STRIP - 1)
-        elif edge == "top":
-            free[:STRIP, :] = True
-            own = (STRIP, 10)
-        else:
-            free[R.SIZE - STRIP:, :] = True
-            own = (R.SIZE - STRIP - 1, 10)
-        g = np.zeros((4, R.SIZE, R.SIZE), dtype=bool)
-        for r, c in np.argwhere(~free):
-            g[1 + (r + c) % 3, r, c] = True
-        g[:, own[0], own[1]] = False
-        g[0, own[0], own[1]] = True
-        out.append(R.make_state(g))
-    return out
-
-
 class OnePly:
     """128 roots (board-major, mover 0..3), their set tables, the 8,192 playout ids, and per
     order the oracle's board after one placement with the move it placed (-1: none)."""
 
     def __init__(self):
-        boards = np.concatenate([R.random_bit_states()[:28]] + strip_states())
+        boards = np.concatenate([R.random_bit_states()[:28]] + [s for _, s in strip_states()])
         assert len(boards) == 32
         self.st = np.repeat(boards, 4)
         self.st["current_player"] = np.tile(np.arange(4, dtype=np.uint8), len(boards))

@@ -18,45 +18,18 @@ import pytest
 from oracle import pyoracle as O
 from reinforcementlearning_blokus_amd import _native as N
 from tests import rules_reference as R
+from tests.edge_boards import STRIP, strip_states
 from tests.helpers import mt_array, oracle_fset, oracle_states, pack_many
 
 pytestmark = pytest.mark.gpu
 
 SEED = 20260311
-STRIP = 3
 
 
 @pytest.fixture(scope="module")
 def gpu():
     from reinforcementlearning_blokus_amd.gpu import BlokusGPU
     return BlokusGPU(0)
-
-
-def strip_states():
-    """[(edge, state)]: opponents own every cell but a STRIP-wide band along one edge; the
-    mover (player 0) owns one cell just outside the band, so the band holds two corner cells."""
-    out = []
-    for edge in ("left", "right", "top", "bottom"):
-        free = np.zeros((R.SIZE, R.SIZE), dtype=bool)
-        if edge == "left":
-            free[:, :STRIP] = True
-            own = (10, STRIP)
-        elif edge == "right":
-            free[:, R.SIZE - STRIP:] = True
-            own = (10, R.SIZE - STRIP - 1)
-        elif edge == "top":
-            free[:STRIP, :] = True
-            own = (STRIP, 10)
-        else:
-            free[R.SIZE - STRIP:, :] = True
-            own = (R.SIZE - STRIP - 1, 10)
-        g = np.zeros((4, R.SIZE, R.SIZE), dtype=bool)
-        for r, c in np.argwhere(~free):
-            g[1 + (r + c) % 3, r, c] = True
-        g[:, own[0], own[1]] = False
-        g[0, own[0], own[1]] = True
-        out.append((edge, R.make_state(g)))
-    return out
 
 
 @pytest.fixture(scope="module")
