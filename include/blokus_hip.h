@@ -333,6 +333,35 @@ int bk_arena_step(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const
                   const uint8_t* seat_masks, const uint8_t* quick_masks, const int32_t* forced,
                   uint32_t* rng_state, bk_result* out, bk_stop_info* stop_out, int mem);
 
+/*
+ * bk_arena_step that also keeps the positions the win-probability dataset wants
+ * (arena_runner.py:625-650: after a successful move whose move_count is a checkpoint).
+ * Bit c of ply_mask (c = 1..127): when a placement of this call makes game i's move_count
+ * c -- a random, heuristic or forced placement alike; passes never capture -- the
+ * position, its frontier tables and the arena's turn count after that placement go to
+ * slot k of game i: states[i * K + k], sets[i * K + k], turn[i * K + k], where k is the
+ * number of mask bits below c and K the mask's popcount.  The stored bk_state is the
+ * position alone (reserved words 0), what bk_rollout_frontier with BK_SEM_ADVANCE and a
+ * budget of c placements returns for the same game.  The slots are the caller's device
+ * memory and persist across calls: the caller sets turn to -1 before the first step, a
+ * slot is written at most once per game (move_count only grows), a BK_FORCE_SKIP game is
+ * not touched, and a slot whose turn is still -1 at the end was never reached.  Ply 0 is
+ * the caller's (every game starts from the empty board): bit 0 must be clear.
+ * BK_MEM_DEVICE only; sets 16-byte, states 8-byte, turn 4-byte aligned.  Kernel:
+ * k_rollout_fr_hs; bk_arena_step's own launch is unchanged.
+ */
+typedef struct bk_snap_plan {        /* POD */
+    uint32_t ply_mask[4];            /* bit c: capture when move_count becomes c (1..127) */
+    bk_state* states;                /* [n][K], K = popcount(ply_mask); device memory     */
+    bk_fset* sets;                   /* [n][K], 16-byte aligned                           */
+    int32_t* turn;                   /* [n][K]; the caller sets -1 before the first step  */
+} bk_snap_plan;
+int bk_arena_step_snap(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const bk_rollout_cfg* cfg,
+                       const uint8_t* seat_masks, const uint8_t* quick_masks, const int32_t* forced,
+                       uint32_t* rng_state, bk_result* out, bk_stop_info* stop_out, const bk_snap_plan* plan,
+                       int mem);
+int bk_snap_plan_size(void);
+
 /* numpy RandomState(seed) cursor for rng_state (host, no GPU) */
 int bk_mt_cursor_init(uint32_t seed, uint32_t* out4);
 

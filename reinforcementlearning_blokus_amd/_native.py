@@ -40,6 +40,7 @@ EXPORTS = (
     "bk_snapshot_features", "bk_snapshot_rec_size",
     "bk_winprob_eval", "bk_winprob_model_size",
     "bk_step_metrics", "bk_step_rec_size",
+    "bk_arena_step_snap", "bk_snap_plan_size",
 )
 # bk_debug_mcts_failure record (include/blokus_hip.h BK_DIAG_*)
 DIAG_WORDS = 64
@@ -79,6 +80,36 @@ class BkRolloutCfg(C.Structure):
     _fields_ = [("semantics", C.c_int32), ("order", C.c_int32), ("rng", C.c_int32), ("max_plies", C.c_int32),
                 ("seed", C.c_uint64), ("seats_share_stream", C.c_int32), ("heuristic_seats", C.c_int32),
                 ("stream_base", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class BkSnapPlan(C.Structure):
+    """bk_snap_plan: the checkpoint plies of bk_arena_step_snap and the caller's device slots."""
+    _fields_ = [("ply_mask", C.c_uint32 * 4), ("states", C.c_void_p), ("sets", C.c_void_p), ("turn", C.c_void_p)]
+
+
+SNAP_MAX_PLY = 127  # the highest ply a bk_snap_plan mask can name (a game has at most 84 placements)
+
+
+def snap_plan_plies(checkpoints):
+    """The plies of `checkpoints` bk_arena_step_snap captures, ascending: slot k of a game
+    belongs to the k-th of them.  Ply 0 is the caller's (every game starts from the empty
+    board), duplicates count once, and plies past SNAP_MAX_PLY can never be reached."""
+    return sorted({int(c) for c in checkpoints if 1 <= int(c) <= SNAP_MAX_PLY})
+
+
+def snap_plan_mask(checkpoints):
+    """bk_snap_plan.ply_mask of `checkpoints`: bit c of the 128 set for each of snap_plan_plies."""
+    mask = [0, 0, 0, 0]
+    for c in snap_plan_plies(checkpoints):
+        mask[c >> 5] |= 1 << (c & 31)
+    return mask
+
+
+def snap_plan_slot(checkpoints, ply: int) -> int:
+    """The slot of checkpoint `ply` (the number of mask bits below it), -1 if the kernel
+    does not capture it."""
+    plies = snap_plan_plies(checkpoints)
+    return plies.index(int(ply)) if int(ply) in plies else -1
 
 
 class BkFastMctsOut(C.Structure):
@@ -293,6 +324,9 @@ def load():
             "bk_winprob_model_size": (C.c_int, []),
             "bk_step_metrics": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int32, vp, C.c_int]),
             "bk_step_rec_size": (C.c_int, []),
+            "bk_arena_step_snap": (C.c_int, [vp, vp, vp, C.c_int32, P(BkRolloutCfg), vp, vp, vp, vp, vp, vp,
+                                             P(BkSnapPlan), C.c_int]),
+            "bk_snap_plan_size": (C.c_int, []),
         }
         for name, (res, args) in sigs.items():
             f = getattr(L, name)
@@ -632,6 +666,15 @@ class Handle:
                                        C.c_void_p(masks_ptr), C.c_void_p(quick_ptr), C.c_void_p(forced_ptr),
                                        C.c_void_p(rng_ptr), C.c_void_p(out_ptr), C.c_void_p(stop_ptr), mem)
         self.check(rc, "bk_arena_step")
+
+    def arena_step_snap(self, states_ptr, sets_ptr, n, cfg: BkRolloutCfg, masks_ptr, quick_ptr, forced_ptr, rng_ptr,
+                        out_ptr, stop_ptr, plan: BkSnapPlan, mem):
+        with self._lock:
+            rc = self._L.bk_arena_step_snap(self._h, C.c_void_p(states_ptr), C.c_void_p(sets_ptr), n, C.byref(cfg),
+                                            C.c_void_p(masks_ptr), C.c_void_p(quick_ptr), C.c_void_p(forced_ptr),
+                                            C.c_void_p(rng_ptr), C.c_void_p(out_ptr), C.c_void_p(stop_ptr),
+                                            C.byref(plan), mem)
+        self.check(rc, "bk_arena_step_snap")
 
     def telemetry(self, states_ptr, sets_ptr, n, cfg: BkTelemetryCfg, out_ptr, mem):
         with self._lock:

@@ -43,8 +43,9 @@ class SnapshotConfig:
     """Snapshot datasets (:90-123): with ``enabled`` the arena captures, at the fixed plies
     ``checkpoints``, one row of win-probability features per player (analytics/winprob) and
     run_experiment writes them as snapshots.csv.  All-random runs replay their games on the
-    GPU to each checkpoint; every other seating plays in the host loop (run_single_game),
-    the batched mixed-agent paths do not capture yet."""
+    GPU to each checkpoint; batchable mixed seatings capture inside the device-resident
+    arena step (bk_arena_step_snap); every other seating plays in the host loop
+    (run_single_game)."""
     enabled: bool = False
     strategy: str = "fixed_ply"
     checkpoints: List[int] = field(default_factory=lambda: list(DEFAULT_SNAPSHOT_PLYS))

@@ -6,10 +6,12 @@ RandomAgent seed (``_agent_seed``), so its record equals ``run_single_game``'s f
 same run seed and game index.  ``run_single_game`` is the reference loop itself
 (:578-777) over the GPU-backed ``BlokusGame`` for every other seating.
 
-With ``snapshots.enabled`` both paths also produce the reference's win-probability rows
+With ``snapshots.enabled`` every path also produces the reference's win-probability rows
 (:522-575, :625-650, :722-731), appended to the list passed as ``snapshot_rows``: the host
-loop captures positions at the checkpoints and ``run_games_gpu`` replays the games to each
-checkpoint; either way the features come from bk_snapshot_features launches
+loop captures positions at the checkpoints, ``run_games_gpu`` replays the games to each
+checkpoint, and ``run_games_batched``'s device driver captures inside its step kernel
+(bk_arena_step_snap: a device-side copy into a per-game slot when a placement reaches a
+checkpoint); the features always come from bk_snapshot_features launches
 (``SnapshotBatch``).  ``run_experiment`` writes them as snapshots.csv.
 """
 from __future__ import annotations
@@ -275,10 +277,43 @@ class SnapshotBatch:
         sets = np.concatenate([self._sets[i] for i in order])
         turns = np.array([self._meta[i]["turn_index"] for i in order], dtype=np.int32)
         recs, feats = BlokusGPU.shared(self.device).snapshot_features(states, sets, turns, self.run_config.max_turns)
-        for k, per_player in zip(order, rows_from_launch(recs, feats)):
-            m = self._meta[k]
+        self._emit([self._meta[k] for k in order], rows_from_launch(recs, feats), rows_out)
+        self._states, self._sets, self._meta, self._labels = [], [], [], {}
+
+    def flush_device(self, gpu, captures: Sequence[Mapping[str, Any]], states, sets, turns,
+                     rows_out: List[Dict[str, Any]]) -> None:
+        """The device-resident entry: positions that never left the GPU.  states / sets / turns
+        are torch CUDA tensors (uint8[m, 256], uint8[m, 2080], int32[m]) and captures[j] names
+        row j's game (run_id, game_index, game_seed, seats, checkpoint_ply); one
+        bk_snapshot_features launch on `gpu`, the rows appended in the order given.  The games'
+        records must have been given to ``label``."""
+        from .. import _native as N
+        from ..analytics.winprob.features import rows_from_launch
+        m = len(captures)
+        if m == 0:
+            return
+        recs_d, feats_d = gpu.snapshot_features(states, sets, turns, self.run_config.max_turns)
+        head = states[:, 240:248].cpu().numpy()  # first_move, current_player, out_mask, flags, move_count
+        recs = recs_d.cpu().numpy().view(N.SNAPSHOT_REC_DTYPE).reshape(m, 4)
+        feats = feats_d.cpu().numpy()
+        turn_h = turns.cpu().numpy()
+        cpi = _checkpoint_index(self.run_config)
+        metas = [{"run_id": c["run_id"], "game_index": int(c["game_index"]), "game_seed": int(c["game_seed"]),
+                  "seats": dict(c["seats"]), "checkpoint_index": cpi[c["checkpoint_ply"]],
+                  "checkpoint_ply": int(c["checkpoint_ply"]), "ply": int(head[j, 4]) | int(head[j, 5]) << 8,
+                  "turn_index": int(turn_h[j]), "current_player_id": int(head[j, 1]) + 1}
+                 for j, c in enumerate(captures)]
+        self._emit(metas, rows_from_launch(recs, feats), rows_out)
+
+    def _emit(self, metas, per_player_rows, rows_out: List[Dict[str, Any]]) -> None:
+        labels: Dict[int, Tuple[List[int], str, str]] = {}  # per game: winners and the two JSON columns
+        for m, per_player in zip(metas, per_player_rows):
             rec = self._labels[m["game_index"]]
-            winner_ids = [int(w) for w in rec["winner_ids"]]
+            if m["game_index"] not in labels:
+                w = [int(x) for x in rec["winner_ids"]]
+                labels[m["game_index"]] = (w, json.dumps(w, sort_keys=True),
+                                           json.dumps(rec["final_scores"], sort_keys=True))
+            winner_ids, winners_json, scores_json = labels[m["game_index"]]
             for player in Player:
                 pid = int(player.value)
                 row: Dict[str, Any] = {
@@ -287,14 +322,13 @@ class SnapshotBatch:
                     "checkpoint_index": m["checkpoint_index"], "checkpoint_ply": m["checkpoint_ply"], "ply": m["ply"],
                     "turn_index": m["turn_index"], "current_player_id": m["current_player_id"], "player_id": pid,
                     "player_name": player.name, "agent_name": m["seats"][str(pid)], "seat_index": pid - 1,
-                    "winner_id": rec["winner_id"], "winner_ids_json": json.dumps(winner_ids, sort_keys=True),
+                    "winner_id": rec["winner_id"], "winner_ids_json": winners_json,
                     "label_is_winner": int(pid in winner_ids), "final_score": int(rec["final_scores"][str(pid)]),
                     "final_rank": int(rec["final_ranks"][str(pid)]),
-                    "final_scores_json": json.dumps(rec["final_scores"], sort_keys=True), "is_tie": bool(rec["is_tie"]),
+                    "final_scores_json": scores_json, "is_tie": bool(rec["is_tie"]),
                 }
                 row.update(per_player[player.name])
                 rows_out.append(row)
-        self._states, self._sets, self._meta, self._labels = [], [], [], {}
 
     def _first_capture(self, game_index: int) -> int:
         return next(i for i, m in enumerate(self._meta) if m["game_index"] == game_index)
@@ -408,15 +442,21 @@ STATUS_CAP = 8  # bk_result.status bit 3 (include/blokus_hip.h)
 
 
 def run_games_gpu(run_config: RunConfig, game_indices: Sequence[int], *, run_id: str = "gpu",
-                  device: int = 0, snapshot_rows: Optional[list] = None) -> List[Dict[str, Any]]:
+                  device: int = 0, snapshot_rows: Optional[list] = None,
+                  snapshot_replay: bool = False) -> List[Dict[str, Any]]:
     """All-random seatings: the games ``game_indices`` in one frontier-order playout launch.
     Per-move times are not observable inside the kernel; each game's duration is its
     share of the launch and per-agent time is split by moves made.
-    With snapshots enabled and ``snapshot_rows`` given, the games -- deterministic in their
-    seeds -- are replayed from the empty board to every checkpoint c > 0 (SEM_ADVANCE with a
-    budget of c placements: the position, its tables and the turn count at the c-th
-    placement), one bk_snapshot_features launch per checkpoint; a game that ended, or was
-    cut by max_turns, before its c-th placement has no row for c."""
+    With snapshots enabled and ``snapshot_rows`` given, the games run as ONE
+    bk_arena_step_snap launch instead (run_games_batched's device driver with no stop seat:
+    the same seat streams, the same games), which captures the checkpoint positions as they
+    are played: 2.3x the end-to-end rate of the replays at 4,096 games
+    (profiles/arena_snapshots).  ``snapshot_replay`` keeps the earlier route, an independent
+    way to the same rows: the games -- deterministic in their seeds -- are replayed from the
+    empty board to every checkpoint c > 0 (SEM_ADVANCE with a budget of c placements: the
+    position, its tables and the turn count at the c-th placement), one
+    bk_snapshot_features launch per checkpoint; a game that ended, or was cut by max_turns,
+    before its c-th placement has no row for c."""
     from .. import _native as N
     from ..gpu import BlokusGPU, empty_state
     if not _all_random(run_config):
@@ -425,6 +465,8 @@ def run_games_gpu(run_config: RunConfig, game_indices: Sequence[int], *, run_id:
     n = len(idx)
     if n == 0:
         return []
+    if run_config.snapshots.enabled and snapshot_rows is not None and not snapshot_replay:
+        return run_games_batched(run_config, idx, run_id=run_id, device=device, snapshot_rows=snapshot_rows)
     seats, seeds, gseeds = [], np.zeros((n, 4), dtype=np.uint32), []
     for i, gi in enumerate(idx):
         gs = game_seed_from_run_seed(run_config.seed, gi)
@@ -779,7 +821,7 @@ def _capture_failed_job(capture_dir: str, job: Dict[str, Any], o, bad, zob_d, lo
 
 def _run_games_device(run_config: RunConfig, idx: List[int], seats: List[Mapping[str, str]], gseeds: List[int],
                       agents_dev, *, run_id: str, device: int, progress=None,
-                      opts: "ArenaOptions") -> List[Dict[str, Any]]:
+                      opts: "ArenaOptions", snapshot_rows: Optional[list] = None) -> List[Dict[str, Any]]:
     """run_games_batched with every position, frontier table and agent stream resident in
     HBM for the whole run.  A round is: bk_arena_step over all games (each first places
     the move its stop seat chose last round, then plays random / heuristic seats to the
@@ -789,12 +831,18 @@ def _run_games_device(run_config: RunConfig, idx: List[int], seats: List[Mapping
     seats; the chosen moves go back as forced moves (a move int, or a list index for
     FastMCTS).  Only results, stop infos and forced moves cross PCIe each round, plus the
     searched positions' 256 bytes for their root Zobrist hash.  Same agents, seeds, streams
-    and move order as run_single_game (arena_runner.py:578-777)."""
+    and move order as run_single_game (arena_runner.py:578-777).
+    With snapshots enabled and ``snapshot_rows`` given, every step is bk_arena_step_snap:
+    the step kernel places every move of the run -- the random and heuristic seats' own, and
+    the search seats' (MCTS, FastMCTS on either path, with or without hand-back) as the
+    next step's forced move -- so each placement that reaches a checkpoint ply leaves its
+    position in the game's device slot, and the rows come from one bk_snapshot_features
+    launch over the slots after the last game (_device_snapshot_rows)."""
     import torch
 
     from .. import _native as N
     from ..agents.fast_mcts_agent import _log_table
-    from ..gpu import BlokusGPU, empty_state, mcts_log_table, mcts_node_cap
+    from ..gpu import BlokusGPU, SnapSlots, empty_state, mcts_log_table, mcts_node_cap
     from ..mcts.mcts_agent import SEARCH_TOTALS
     mcts, fast, seat_kind, seat_agent = agents_dev
     n = len(idx)
@@ -832,6 +880,10 @@ def _run_games_device(run_config: RunConfig, idx: List[int], seats: List[Mapping
     forced_d = torch.full((n,), -1, dtype=torch.int32, device=dev)
     out_d = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
     stop_d = torch.zeros((n, N.STOP_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    snap_on = run_config.snapshots.enabled and snapshot_rows is not None
+    # the games' checkpoint slots (K x 2,340 bytes per game); ply 0 is filled in at the end
+    slots = (SnapSlots.allocate(n, run_config.snapshots.checkpoints, device)
+             if snap_on and N.snap_plan_plies(run_config.snapshots.checkpoints) else None)
     # MCTS agents: Zobrist tables, rollout streams and TTs (one row each) on the device
     am = len(mcts)
     if am:
@@ -1156,7 +1208,7 @@ def _run_games_device(run_config: RunConfig, idx: List[int], seats: List[Mapping
                 progress(prof["rounds"], int(active.sum()), prof)
             ta = time.perf_counter()
             gpu.arena_step(states_d, sets_d, masks_d, rng_d, quick_d, forced_d, out_d, stop_d,
-                           max_turns=run_config.max_turns)
+                           max_turns=run_config.max_turns, snap=slots)
             # one copy back per step: results, stop infos, the player to move
             step_h = torch.cat([out_d, stop_d, states_d[:, 240:244]], dim=1).cpu().numpy()
             res = np.ascontiguousarray(step_h[:, :32]).view(N.RESULT_DTYPE).reshape(n)
@@ -1288,7 +1340,74 @@ def _run_games_device(run_config: RunConfig, idx: List[int], seats: List[Mapping
     finally:
         if gc_on:
             gc.enable()
+    if snap_on:
+        ts = time.perf_counter()
+        _device_snapshot_rows(gpu, run_config, idx, seats, gseeds, out, slots, run_id, device, snapshot_rows)
+        prof["snapshot_rows_s"] = time.perf_counter() - ts  # gather, feature launch, rows (host)
     return out
+
+
+def _host_loop_with_rows(run_config, idx, seats, gseeds, run_id, device, snapshot_rows) -> List[Dict[str, Any]]:
+    """run_games_batched asked for snapshot rows where only the host-staged rounds could
+    play: the games through run_single_game, their rows from one launch."""
+    agent_configs = {a.name: a for a in run_config.agents}
+    batch = SnapshotBatch(run_config, device)
+    out = [run_single_game(run_id=run_id, game_index=gi, game_seed=gs, run_config=run_config, seat_assignment=st,
+                           agent_configs=agent_configs, snapshot_batch=batch)
+           for gi, st, gs in zip(idx, seats, gseeds)]
+    batch.flush(snapshot_rows)
+    return out
+
+
+def _device_snapshot_rows(gpu, run_config, idx, seats, gseeds, records, slots, run_id, device, snapshot_rows) -> None:
+    """The snapshot rows of _run_games_device's finished games: the slots the step kernel
+    filled (turn >= 0) are gathered on the device, the ply-0 checkpoint -- every game starts
+    from the empty board with Board()'s tables, at turn 0 -- is added here, and one
+    bk_snapshot_features launch makes the rows, labelled from the records and ordered by
+    (game, checkpoint_index, player_id) as run_games_gpu orders them.  Also fills each
+    record's snapshot_checkpoints_hit."""
+    import torch
+
+    from .. import _native as N
+    from ..gpu import empty_state
+    n = len(idx)
+    dev = torch.device("cuda", device)
+    hits: List[List[int]] = [[] for _ in idx]
+    caps: List[Dict[str, Any]] = []
+    st_parts, fs_parts, turn_parts = [], [], []
+
+    def capture(i, ply):
+        hits[i].append(ply)
+        caps.append({"run_id": run_id, "game_index": idx[i], "game_seed": gseeds[i], "seats": seats[i],
+                     "checkpoint_ply": ply})
+
+    if 0 in run_config.snapshots.checkpoints:
+        st_parts.append(torch.from_numpy(empty_state().view(np.uint8).reshape(1, 256)).to(dev).expand(n, 256))
+        fs_parts.append(torch.from_numpy(N.fset_new(1).view(np.uint8).reshape(1, -1)).to(dev).expand(n, -1))
+        turn_parts.append(torch.zeros(n, dtype=torch.int32, device=dev))
+        for i in range(n):
+            capture(i, 0)
+    if slots is not None:
+        k = len(slots.plies)
+        sel = np.flatnonzero(slots.turn.cpu().numpy().reshape(-1) >= 0)  # (game, ply) ascending
+        if len(sel):
+            sel_d = torch.from_numpy(sel).to(dev)
+            st_parts.append(slots.states.view(n * k, 256).index_select(0, sel_d))
+            fs_parts.append(slots.sets.view(n * k, -1).index_select(0, sel_d))
+            turn_parts.append(slots.turn.view(-1).index_select(0, sel_d))
+            for j in sel.tolist():
+                capture(j // k, slots.plies[j % k])
+    batch = SnapshotBatch(run_config, device)
+    for rec, h in zip(records, hits):
+        rec["snapshot_checkpoints_hit"] = sorted(h)
+        batch.label(rec)
+    rows: List[Dict[str, Any]] = []
+    if caps:
+        batch.flush_device(gpu, caps, torch.cat(st_parts).contiguous(), torch.cat(fs_parts).contiguous(),
+                           torch.cat(turn_parts).contiguous(), rows)
+    pos = {gi: i for i, gi in enumerate(idx)}
+    rows.sort(key=lambda r: (pos[r["game_index"]], r["checkpoint_index"], r["player_id"]))
+    snapshot_rows.extend(rows)
 
 
 def _device_records(out, idx, results, per_agent, final, seats, gseeds, run_config, run_id, dt, n):
@@ -1356,7 +1475,7 @@ MAX_SEARCH_STREAMS = 16
 
 def run_games_batched(run_config: RunConfig, game_indices: Sequence[int], *, run_id: str = "gpu",
                       device: int = 0, progress=None, options: Optional[ArenaOptions] = None,
-                      **option_kw) -> List[Dict[str, Any]]:
+                      snapshot_rows: Optional[list] = None, **option_kw) -> List[Dict[str, Any]]:
     """Mixed seatings (Random / Heuristic / MCTS / FastMCTS, config 4) in lockstep batches:
     every game's random and heuristic turns run inside bk_arena_advance (one launch
     advances all games to their next search-seat turn, each seat drawing from its own
@@ -1366,7 +1485,13 @@ def run_games_batched(run_config: RunConfig, game_indices: Sequence[int], *, run
     equal run_single_game's (arena_runner.py:578-777): same agents, seeds, streams and
     move order.  Per-move times are launch shares.  progress(round, games_left, profile),
     if given, is called at the start of every round.  options (or the same fields as
-    keywords, e.g. search_streams=4): ArenaOptions."""
+    keywords, e.g. search_streams=4): ArenaOptions.
+    With snapshots enabled and ``snapshot_rows`` given, the device-resident driver captures
+    the checkpoint positions inside its step kernel and appends the games' rows (ordered by
+    game, checkpoint, player) to snapshot_rows, filling snapshot_checkpoints_hit.  The
+    host-staged rounds (device_driver=False, or agents the device driver cannot carry) do
+    not capture: asked for rows, such a call plays its games through run_single_game with
+    one SnapshotBatch instead (the same records and rows, one game at a time)."""
     from .. import _native as N
     from ..engine.move_generator import frontier_ranks, order_moves, order_moves_many
     from ..engine.pieces import ORIENT_CELLS, ORIENT_LIST
@@ -1381,6 +1506,13 @@ def run_games_batched(run_config: RunConfig, game_indices: Sequence[int], *, run
         options = ArenaOptions(**option_kw)
     elif option_kw:
         raise TypeError("pass ArenaOptions or its fields as keywords, not both")
+    snap_on = run_config.snapshots.enabled and snapshot_rows is not None
+    if snap_on and not options.device_driver:
+        seats_h, gseeds_h = [], []
+        for gi in idx:
+            gseeds_h.append(game_seed_from_run_seed(run_config.seed, gi))
+            seats_h.append(seat_assignment_for_game(run_config.agent_names, gi, gseeds_h[-1], run_config.seat_policy))
+        return _host_loop_with_rows(run_config, idx, seats_h, gseeds_h, run_id, device, snapshot_rows)
     if options.device_driver:
         t_in = time.perf_counter()
         seats_d, gseeds_d = [], []
@@ -1404,11 +1536,14 @@ def run_games_batched(run_config: RunConfig, game_indices: Sequence[int], *, run
         finally:
             if gc_on:
                 gc.enable()
+        if ag is None and snap_on:
+            return _host_loop_with_rows(run_config, idx, seats_d, gseeds_d, run_id, device, snapshot_rows)
         if ag is not None:
             agents_s = time.perf_counter() - t_in
             setup_gc = sum(g["collections"] for g in gc.get_stats()) - gc0
             out = _run_games_device(run_config, idx, seats_d, gseeds_d, ag, run_id=run_id, device=device,
-                                    progress=progress, opts=options)
+                                    progress=progress, opts=options,
+                                    snapshot_rows=snapshot_rows if snap_on else None)
             # host time around the device loop: seats + agents before it, records after it
             LAST_BATCH_PROFILE.update(agents_s=agents_s, seats_s=t_seats - t_in, agents_gc=setup_gc,
                                       records_s=time.perf_counter() - LAST_BATCH_PROFILE["t_end"],
@@ -1641,13 +1776,12 @@ def run_experiment(run_config: RunConfig, *, verbose: bool = False, device: int 
     if _all_random(run_config):
         records = run_games_gpu(run_config, mine, run_id="pending", device=device,
                                 snapshot_rows=snapshot_rows if snap_on else None)
-    elif not snap_on and batched and all(_batchable(run_config, seat_assignment_for_game(
+    elif batched and all(_batchable(run_config, seat_assignment_for_game(
             run_config.agent_names, gi, game_seed_from_run_seed(run_config.seed, gi), run_config.seat_policy))
             for gi in mine):
-        records = run_games_batched(run_config, mine, run_id="pending", device=device)
+        records = run_games_batched(run_config, mine, run_id="pending", device=device,
+                                    snapshot_rows=snapshot_rows if snap_on else None)
     else:
-        # (with snapshots the batched mixed-agent paths are not used: capture inside
-        # bk_arena_step is a follow-up)
         agent_configs = {a.name: a for a in run_config.agents}
         records = []
         batch = SnapshotBatch(run_config, device) if snap_on else None

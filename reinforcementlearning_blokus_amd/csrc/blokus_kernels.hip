@@ -71,6 +71,7 @@
 #define BK_U_TELEMETRY 12
 #define BK_U_SNAPSHOT 13
 #define BK_U_STEPLOG 14
+#define BK_U_ROLLOUT_FRHS 15
 #ifndef BK_TU
 #define BK_TU 0
 #endif
@@ -2790,9 +2791,11 @@ __device__ __forceinline__ int board_score(const Game& g, int p) {  // p per-lan
     return (int)g.cells.get(p) + ((g.used.get(p) == 0x1FFFFFu) ? 15 : 0);
 }
 
-// write the lane's board back as a bk_state (BK_SEM_ADVANCE)
-__device__ __forceinline__ void store_state(const RolloutArgs& a, const Game& g, const Slab& slab) {
-    bk_state* o = a.out_states + g.pid;
+// write the lane's board as a bk_state to o (BK_SEM_ADVANCE: a.out_states + g.pid).  COUNTS
+// false (a snapshot slot): the position alone, reserved words 0 as a BK_SEM_ADVANCE replay
+// of the game leaves them
+template <bool COUNTS = true>
+__device__ __forceinline__ void store_state(const RolloutArgs& a, const Game& g, const Slab& slab, bk_state* o) {
 #pragma unroll 1
     for (int p = 0; p < 4; ++p) {
         uint64_t w[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -2815,8 +2818,8 @@ __device__ __forceinline__ void store_state(const RolloutArgs& a, const Game& g,
     o->move_count = (uint16_t)(g.move_count0 + g.plies);
     o->reserved16 = 0;
     // bk_arena_advance: the game's arena turn_count / passes so far (raw, see finish_game)
-    o->reserved[0] = a.seat_masks ? g.turns0 + (uint32_t)g.turns : 0u;
-    o->reserved[1] = a.seat_masks ? g.passes0 + (uint32_t)g.passes : 0u;
+    o->reserved[0] = COUNTS && a.seat_masks ? g.turns0 + (uint32_t)g.turns : 0u;
+    o->reserved[1] = COUNTS && a.seat_masks ? g.passes0 + (uint32_t)g.passes : 0u;
 }
 
 // player p's table header in the rollout slab (frontier order): (mask, fill, used) as three
@@ -3001,7 +3004,7 @@ __device__ __forceinline__ void finish_game(const RolloutArgs& a, Game& g, const
         for (int q = 0; q < 4; ++q) reinterpret_cast<uint4*>(a.rng_io + (size_t)g.pid * 16)[q] = t[q];
     }
     if (a.out_states != nullptr) {  // BK_SEM_ADVANCE, or an arena run that wants final states
-        store_state(a, g, slab);
+        store_state(a, g, slab, a.out_states + g.pid);
         if constexpr (FR) copy_fset_out(a.out_sets + g.pid, &a.fslab[slot].s, slab);
         if (a.out == nullptr) { g.pid = -1; return; }
     }
@@ -3276,8 +3279,39 @@ __device__ __forceinline__ void stop_info(const RolloutArgs& a, const Game& g, c
 #define HEUR_WORDS (84 * WAVE)
 #define HEUR_PSUM 40  // dword offset of the per-piece sums in a wave's area
 
-template <bool FR, bool HEUR = false>
-__device__ __forceinline__ void rollout_body(const RolloutArgs& a) {
+// bk_arena_step_snap's plan as k_rollout_fr_hs takes it (a kernel argument of its own: the
+// other kernels' RolloutArgs, and so their code objects, stay as they are).  Bit c of
+// ply_mask: the placement that makes move_count c is captured, into slot (number of mask
+// bits below c) of the game's k slots
+struct CaptureArgs {
+    uint32_t ply_mask[4];
+    uint32_t k;
+    bk_state* states;  // [n_playouts][k]
+    bk_fset* sets;     // [n_playouts][k]
+    int32_t* turn;     // [n_playouts][k]
+};
+
+// SNAP (k_rollout_fr_hs): the lane's position, tables and turn count after a placement that
+// reaches a checkpoint ply go to the game's slot for it.  Per-lane stores, rare (<= k per game)
+__device__ __forceinline__ void capture_checkpoint(const RolloutArgs& a, const CaptureArgs& sn, const Game& g,
+                                                   const Slab& slab, uint32_t slot) {
+    const uint32_t c = g.move_count0 + (uint32_t)g.plies;
+    if (c >= 128u) return;
+    const uint32_t w = c >> 5, below = (1u << (c & 31u)) - 1u;
+    const uint32_t m0 = sn.ply_mask[0], m1 = sn.ply_mask[1], m2 = sn.ply_mask[2], m3 = sn.ply_mask[3];
+    const uint32_t mw = w == 0u ? m0 : (w == 1u ? m1 : (w == 2u ? m2 : m3));
+    if (!((mw >> (c & 31u)) & 1u)) return;
+    const uint32_t k = (uint32_t)__builtin_popcount(mw & below) + (w > 0u ? (uint32_t)__builtin_popcount(m0) : 0u) +
+                       (w > 1u ? (uint32_t)__builtin_popcount(m1) : 0u) +
+                       (w > 2u ? (uint32_t)__builtin_popcount(m2) : 0u);
+    const size_t at = (size_t)g.pid * sn.k + k;  // k < sn.k: bit c is set and k counts the bits below it
+    store_state<false>(a, g, slab, sn.states + at);
+    copy_fset_out(sn.sets + at, &a.fslab[slot].s, slab);
+    sn.turn[at] = (int32_t)(g.turns0 + (uint32_t)g.turns);
+}
+
+template <bool FR, bool HEUR = false, bool SNAP = false>
+__device__ __forceinline__ void rollout_body(const RolloutArgs& a, const CaptureArgs& sn = CaptureArgs{}) {
     constexpr int BLK = HEUR ? HBLOCK : BLOCK;
     constexpr int AREA = HEUR ? HEUR_WORDS : FR ? ROLL_WORDS_FR : ROLL_WORDS_PER_WAVE;
     constexpr int HS_WORDS = HEUR ? (int)(sizeof(HeurShared) + 7) / 4 : 0;
@@ -3582,6 +3616,9 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a) {
         g.first &= ~(1u << p);
         g.plies++; g.turns++; g.since_move = 0;
         g.cur = (g.cur + 1) & 3;
+        if constexpr (SNAP) {  // (a table that overflowed is no position to keep: the game stops below)
+            if (!(g.status & 2u)) capture_checkpoint(a, sn, g, slab, slot);
+        }
         if constexpr (FR) {
             if (g.status & 2u) finish_game<FR>(a, g, slab, slot);  // status 2: table overflow
         }
@@ -3612,6 +3649,14 @@ __global__ void k_rollout_fr(RolloutArgs a);
 __global__ __launch_bounds__(HBLOCK, 2) void k_rollout_fr_h(RolloutArgs a) { rollout_body<true, true>(a); }
 #else
 __global__ void k_rollout_fr_h(RolloutArgs a);
+#endif
+// k_rollout_fr_h that also captures checkpoint positions (bk_arena_step_snap)
+#if BK_DEF(BK_U_ROLLOUT_FRHS)
+__global__ __launch_bounds__(HBLOCK, 2) void k_rollout_fr_hs(RolloutArgs a, CaptureArgs sn) {
+    rollout_body<true, true, true>(a, sn);
+}
+#else
+__global__ void k_rollout_fr_hs(RolloutArgs a, CaptureArgs sn);
 #endif
 
 // ------------------------------------------------------------------------------------
@@ -7188,7 +7233,8 @@ static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, 
                            bk_result* out, bk_state* out_states, int mem, const bk_fset* root_sets = nullptr,
                            bk_fset* out_sets = nullptr, const uint8_t* seat_masks = nullptr,
                            uint32_t* rng_io = nullptr, const uint8_t* quick_masks = nullptr,
-                           const int32_t* forced = nullptr, bk_stop_info* stop_out = nullptr) {
+                           const int32_t* forced = nullptr, bk_stop_info* stop_out = nullptr,
+                           const bk_snap_plan* plan = nullptr) {
     if (!h || !roots || !cfg || n_roots <= 0 || n_playouts < 0 || (mem != BK_MEM_HOST && mem != BK_MEM_DEVICE))
         return set_err(h, BK_EINVAL, "bk_rollout: invalid arguments%s", "");
     if (cfg->semantics != BK_SEM_ARENA && cfg->semantics != BK_SEM_ROLLOUT && cfg->semantics != BK_SEM_ADVANCE)
@@ -7280,7 +7326,12 @@ static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, 
         int64_t ls = rest <= 0 ? 0 : rest >= (int64_t)nslots ? (int64_t)nslots : ((rest + WAVE - 1) / WAVE) * WAVE;
         a.long_slots = (uint32_t)ls;
     }
-    if (heur) BK_LAUNCH(h, k_rollout_fr_h, dim3(blocks), dim3(HBLOCK), a);
+    if (heur && plan) {  // bk_arena_step_snap (device memory: the slots are the caller's)
+        CaptureArgs sn{{plan->ply_mask[0], plan->ply_mask[1], plan->ply_mask[2], plan->ply_mask[3]}, 0u,
+                       plan->states, plan->sets, plan->turn};
+        for (int w = 0; w < 4; ++w) sn.k += (uint32_t)__builtin_popcount(sn.ply_mask[w]);
+        BK_LAUNCH(h, k_rollout_fr_hs, dim3(blocks), dim3(HBLOCK), a, sn);
+    } else if (heur) BK_LAUNCH(h, k_rollout_fr_h, dim3(blocks), dim3(HBLOCK), a);
     else if (fr) BK_LAUNCH(h, k_rollout_fr, dim3(blocks), dim3(BLOCK), a);
     else if (cfg->semantics == BK_SEM_ADVANCE) BK_LAUNCH(h, k_advance, dim3(blocks), dim3(BLOCK), a);
     else BK_LAUNCH(h, k_rollout, dim3(blocks), dim3(BLOCK), a);
@@ -7539,6 +7590,36 @@ int bk_arena_step(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const
     if (n == 0) return BK_OK;
     return launch_playouts(h, states, n, nullptr, n, cfg, nullptr, out, states, mem, sets, sets, seat_masks,
                            rng_state, quick_masks, forced, stop_out);
+}
+
+int bk_snap_plan_size(void) { return (int)sizeof(bk_snap_plan); }
+
+int bk_arena_step_snap(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const bk_rollout_cfg* cfg,
+                       const uint8_t* seat_masks, const uint8_t* quick_masks, const int32_t* forced,
+                       uint32_t* rng_state, bk_result* out, bk_stop_info* stop_out, const bk_snap_plan* plan, int mem) {
+    if (!h || !states || !sets || !cfg || !seat_masks || !rng_state || !out || n < 0)
+        return set_err(h, BK_EINVAL, "bk_arena_step_snap: invalid arguments%s", "");
+    if (mem != BK_MEM_DEVICE)
+        return set_err(h, BK_EINVAL, "bk_arena_step_snap: BK_MEM_DEVICE only (the slots persist across steps)%s", "");
+    if (!plan || !plan->states || !plan->sets || !plan->turn)
+        return set_err(h, BK_EINVAL, "bk_arena_step_snap: a plan with states, sets and turn%s", "");
+    if (((uintptr_t)plan->sets & 15) || ((uintptr_t)plan->states & 7) || ((uintptr_t)plan->turn & 3))
+        return set_err(h, BK_EINVAL, "bk_arena_step_snap: the plan's sets must be 16-byte, states 8-byte, turn 4-byte "
+                                     "aligned%s", "");
+    if (!(plan->ply_mask[0] | plan->ply_mask[1] | plan->ply_mask[2] | plan->ply_mask[3]))
+        return set_err(h, BK_EINVAL, "bk_arena_step_snap: the ply mask is empty%s", "");
+    if (plan->ply_mask[0] & 1u)
+        return set_err(h, BK_EINVAL, "bk_arena_step_snap: ply 0 is not captured here (the caller fills that slot)%s", "");
+    if (cfg->semantics != BK_SEM_ARENA || cfg->order != BK_ORDER_FRONTIER || cfg->rng != BK_RNG_NUMPY_MT ||
+        cfg->seats_share_stream)
+        return set_err(h, BK_EINVAL, "bk_arena_step_snap: needs ARENA, FRONTIER order, NUMPY_MT per-seat streams%s", "");
+    if (quick_masks && !stop_out)
+        return set_err(h, BK_EINVAL, "bk_arena_step_snap: quick_masks goes with stop_out%s", "");
+    if ((uintptr_t)rng_state & 15)
+        return set_err(h, BK_EINVAL, "bk_arena_step_snap: rng_state must be 16-byte aligned%s", "");
+    if (n == 0) return BK_OK;
+    return launch_playouts(h, states, n, nullptr, n, cfg, nullptr, out, states, mem, sets, sets, seat_masks,
+                           rng_state, quick_masks, forced, stop_out, plan);
 }
 
 int bk_rollout_frontier(bk_handle h, const bk_state* roots, const bk_fset* root_sets, int32_t n_roots,

@@ -432,13 +432,25 @@ class BlokusGPU:
         return out
 
     def arena_step(self, states, sets, seat_masks, rng_state, quick_masks, forced, out, stop_out, *,
-                   max_turns: int = 2500):
+                   max_turns: int = 2500, snap: "SnapSlots | None" = None):
         """bk_arena_step on device tensors, in place (BK_MEM_DEVICE, torch's current
         stream): states uint8[n,256], sets uint8[n,2080], seat_masks / quick_masks uint8[n],
         forced int32[n], rng_state int32[n,16], out uint8[n,32], stop_out uint8[n,16]
-        (STOP_DTYPE).  No position or table crosses PCIe (config 4's device driver)."""
+        (STOP_DTYPE).  No position or table crosses PCIe (config 4's device driver).
+        snap (SnapSlots): bk_arena_step_snap instead -- the same step, and every placement
+        that reaches one of snap.plies leaves its position, tables and turn count in the
+        game's slot for that ply (k_rollout_fr_hs)."""
         import torch
         n = states.shape[0]
+        if snap is not None:
+            k = len(snap.plies)
+            if k == 0 or snap.plies != N.snap_plan_plies(snap.plies):
+                raise ValueError(f"snap.plies: expected ascending distinct plies in 1..{N.SNAP_MAX_PLY}, "
+                                 f"got {snap.plies}")
+            for t, name, dt, shape in ((snap.states, "snap.states", torch.uint8, (n, k, 256)),
+                                       (snap.sets, "snap.sets", torch.uint8, (n, k, N.FSET_DTYPE.itemsize)),
+                                       (snap.turn, "snap.turn", torch.int32, (n, k))):
+                _check_device_tensor(t, name, dt, shape, self.device)
         for t, name, dt, shape in ((states, "states", torch.uint8, (n, 256)),
                                    (sets, "sets", torch.uint8, (n, N.FSET_DTYPE.itemsize)),
                                    (seat_masks, "seat_masks", torch.uint8, (n,)),
@@ -451,6 +463,14 @@ class BlokusGPU:
         if n == 0:
             return
         self._stream_from_torch()
+        if snap is not None:
+            import ctypes as C
+            plan = N.BkSnapPlan((C.c_uint32 * 4)(*N.snap_plan_mask(snap.plies)), snap.states.data_ptr(),
+                                snap.sets.data_ptr(), snap.turn.data_ptr())
+            self.handle.arena_step_snap(states.data_ptr(), sets.data_ptr(), n, cfg, seat_masks.data_ptr(),
+                                        quick_masks.data_ptr(), forced.data_ptr(), rng_state.data_ptr(),
+                                        out.data_ptr(), stop_out.data_ptr(), plan, N.MEM_DEVICE)
+            return
         self.handle.arena_step(states.data_ptr(), sets.data_ptr(), n, cfg, seat_masks.data_ptr(),
                                quick_masks.data_ptr(), forced.data_ptr(), rng_state.data_ptr(), out.data_ptr(),
                                stop_out.data_ptr(), N.MEM_DEVICE)
@@ -701,6 +721,28 @@ class BlokusGPU:
         if bad:
             raise RuntimeError(f"bk_mcts: {bad} searches stopped early, status bits "
                                f"{sorted(set(st[st != 0].tolist()))[:8]}")
+
+
+class SnapSlots:
+    """The checkpoint slots of n games for arena_step(snap=...): ``plies`` the plies the
+    kernel captures (ascending, 1..127: _native.snap_plan_plies of the run's checkpoints),
+    and per game and ply a bk_state (states uint8[n, K, 256]), a bk_fset (sets
+    uint8[n, K, 2080]) and the arena's turn count at the capture (turn int32[n, K], -1 =
+    not reached), all torch CUDA tensors that stay on the device across the steps."""
+
+    def __init__(self, plies, states, sets, turn):
+        self.plies, self.states, self.sets, self.turn = list(plies), states, sets, turn
+
+    @classmethod
+    def allocate(cls, n: int, checkpoints, device: int = 0) -> "SnapSlots":
+        """Empty slots (turn -1) for the plies of `checkpoints` the kernel captures."""
+        import torch
+        plies = N.snap_plan_plies(checkpoints)
+        dev = torch.device("cuda", device)
+        k = len(plies)
+        return cls(plies, torch.zeros((n, k, 256), dtype=torch.uint8, device=dev),
+                   torch.zeros((n, k, N.FSET_DTYPE.itemsize), dtype=torch.uint8, device=dev),
+                   torch.full((n, k), -1, dtype=torch.int32, device=dev))
 
 
 def _stream_base(base: int, n: int) -> int:
