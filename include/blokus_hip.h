@@ -572,6 +572,7 @@ int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const 
 #define BK_DIAG_K_H 2         /* k_mcts_h    */
 #define BK_DIAG_K_COOP 3      /* k_mcts_coop */
 #define BK_DIAG_K_COOP_H 4    /* k_mcts_coop_h */
+#define BK_DIAG_K_COOP_L 5    /* k_mcts_coop_l (bk_mcts_learned) */
 int bk_debug_mcts_failure(bk_handle h, uint32_t* out, int32_t n);
 
 /*
@@ -739,6 +740,37 @@ int bk_winprob_model_size(void);
 int bk_winprob_eval(bk_handle h, const bk_state* states, const bk_fset* sets, int32_t n,
                     const int32_t* turn_index, int32_t max_turns, const bk_winprob_model* model,
                     double* prob, double* pair_logit, uint8_t* status, int mem);
+
+/*
+ * bk_mcts_learned -- bk_mcts searches whose simulations are learned leaf evaluations
+ * (mcts/mcts_agent.py:408-468 with leaf_evaluation_enabled, optionally
+ * progressive_bias_enabled), whole in one launch (k_mcts_coop_l, one wave per search; added
+ * within ABI 7: new symbols only).  Selection, expansion, the TT and backpropagation are
+ * bk_mcts's; where a rollout would start, the new node's board is evaluated for the node's
+ * player with `model` exactly as bk_winprob_eval evaluates it (turn_index = move_count = the
+ * root's move_count + depth, `max_turns`): the reward, stored in the TT as a rollout reward
+ * is, equals bk_winprob_eval's prob for that board bit for bit.  A terminal node is evaluated
+ * the same way on its own board.  There is no rollout stream: the arguments are bk_mcts's
+ * without mt_state; cfg->max_rollout_moves and cfg->rollout_policy are ignored, cfg->flags
+ * must be 0 (no BK_MCTS_ASYNC / BK_MCTS_STATE_ROWS).
+ * bias_weight != 0: every expansion also sets prior_bias(child) = V(child, parent's player) -
+ * V(parent, parent's player) in prior_bias[g * node_cap + node] (indexed as the node pool)
+ * and selection adds bias_weight * (prior_bias / (1.0 + visits)) after exploit + explore
+ * (MCTSNode.ucb1_value).  prior_bias may be NULL when bias_weight is 0.
+ * bias_updates[g] (required) counts search g's progressive-bias updates.  In out[g],
+ * rollouts counts the leaf evaluations and rollout_plies stays 0.
+ * cfg->iter_stop / resume chunks carry nodes, prior_bias, bias_updates, out and the TT from
+ * launch to launch.  BK_EINVAL before any GPU work: a null required pointer, a non-finite
+ * model value or bias weight, a scale of 0, max_turns < 0, node_cap < 1, a tt_cap that is no
+ * power of two, log_len < 1.  An invalid board inside a search (a non-zero snapshot status)
+ * sets BK_MCTS_EINTERNAL.  The failure record is bk_mcts's, with BK_DIAG_K_COOP_L.
+ */
+int bk_mcts_learned(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const uint8_t* players,
+                    const uint64_t* root_hash, int32_t n_games, const bk_mcts_cfg* cfg, const uint64_t* zobrist,
+                    int32_t n_zobrist, const int32_t* zobrist_index, uint64_t* tt_keys, double* tt_vals,
+                    int32_t* tt_count, const double* log_table, int32_t log_len, const bk_winprob_model* model,
+                    int32_t max_turns, double bias_weight, double* prior_bias, int32_t* bias_updates,
+                    bk_mcts_node* nodes, double* rewards, uint8_t* hit_flags, bk_mcts_out* out, int mem);
 
 /*
  * bk_step_metrics -- the integers behind one line of the strategy step log

@@ -41,10 +41,11 @@ EXPORTS = (
     "bk_winprob_eval", "bk_winprob_model_size",
     "bk_step_metrics", "bk_step_rec_size",
     "bk_arena_step_snap", "bk_snap_plan_size",
+    "bk_mcts_learned",
 )
 # bk_debug_mcts_failure record (include/blokus_hip.h BK_DIAG_*)
 DIAG_WORDS = 64
-DIAG_KERNELS = ("k_mcts", "k_mcts_pair", "k_mcts_h", "k_mcts_coop", "k_mcts_coop_h")
+DIAG_KERNELS = ("k_mcts", "k_mcts_pair", "k_mcts_h", "k_mcts_coop", "k_mcts_coop_h", "k_mcts_coop_l")
 # bk_set_tuning keys (include/blokus_hip.h BK_TUNE_*), by the environment variable name
 # bk_create reads each from once
 TUNE_KEYS = {name: i for i, name in enumerate((
@@ -327,6 +328,9 @@ def load():
             "bk_arena_step_snap": (C.c_int, [vp, vp, vp, C.c_int32, P(BkRolloutCfg), vp, vp, vp, vp, vp, vp,
                                              P(BkSnapPlan), C.c_int]),
             "bk_snap_plan_size": (C.c_int, []),
+            "bk_mcts_learned": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, P(BkMctsCfg), vp, C.c_int32, vp, vp, vp, vp,
+                                          vp, C.c_int32, P(BkWinprobModel), C.c_int32, C.c_double, vp, vp, vp, vp,
+                                          vp, vp, C.c_int]),
         }
         for name, (res, args) in sigs.items():
             f = getattr(L, name)
@@ -652,6 +656,18 @@ class Handle:
                                  v(ttc_ptr), v(log_ptr), log_len, v(nodes_ptr), v(rewards_ptr), v(flags_ptr),
                                  v(out_ptr), mem)
         self.check(rc, "bk_mcts")
+
+    def mcts_learned(self, roots_ptr, sets_ptr, players_ptr, hash_ptr, n_games, cfg: BkMctsCfg, zob_ptr, n_zob,
+                     zidx_ptr, ttk_ptr, ttv_ptr, ttc_ptr, log_ptr, log_len, model: BkWinprobModel, max_turns,
+                     bias_weight, prior_ptr, bias_updates_ptr, nodes_ptr, rewards_ptr, flags_ptr, out_ptr, mem):
+        v = lambda x: C.c_void_p(x or 0)  # noqa: E731
+        with self._lock:
+            rc = self._L.bk_mcts_learned(self._h, v(roots_ptr), v(sets_ptr), v(players_ptr), v(hash_ptr), n_games,
+                                         C.byref(cfg), v(zob_ptr), n_zob, v(zidx_ptr), v(ttk_ptr), v(ttv_ptr),
+                                         v(ttc_ptr), v(log_ptr), log_len, C.byref(model), int(max_turns),
+                                         float(bias_weight), v(prior_ptr), v(bias_updates_ptr), v(nodes_ptr),
+                                         v(rewards_ptr), v(flags_ptr), v(out_ptr), mem)
+        self.check(rc, "bk_mcts_learned")
 
     def arena_advance(self, states_ptr, sets_ptr, n, cfg: BkRolloutCfg, masks_ptr, rng_ptr, out_ptr, mem):
         with self._lock:

@@ -111,7 +111,8 @@ class _GameplayFastMCTSAdapter:
 def build_agent(config: AgentConfig, seed: int):
     """Agent adapter from configuration (:415-492).  ``mcts`` seats search with the
     reference's default HeuristicAgent rollouts; the learned-evaluator options are forwarded
-    as the reference's runner forwards them (MCTSAgent then searches on its "exact" backend)."""
+    as the reference's runner forwards them (MCTSAgent then searches on its "exact" backend,
+    or on the one ``rollout_backend`` names)."""
     kind = config.type.lower()
     params = dict(config.params)
     if kind == "random":
@@ -143,7 +144,8 @@ def build_agent(config: AgentConfig, seed: int):
             potential_shaping_gamma=float(params.get("potential_shaping_gamma", 1.0)),
             potential_shaping_weight=float(params.get("potential_shaping_weight", 1.0)),
             potential_mode=str(params.get("potential_mode", "prob")),
-            max_rollout_moves=int(params.get("max_rollout_moves", 50))))
+            max_rollout_moves=int(params.get("max_rollout_moves", 50)),
+            rollout_backend=params.get("rollout_backend")))  # e.g. "leaf": leaf evaluation in the search kernel
     if kind == "fast_mcts":
         default_time = (float(config.thinking_time_ms) / 1000.0 if config.thinking_time_ms is not None
                         else float(params.get("time_limit", 0.1)))

@@ -72,6 +72,7 @@
 #define BK_U_SNAPSHOT 13
 #define BK_U_STEPLOG 14
 #define BK_U_ROLLOUT_FRHS 15
+#define BK_U_COOP_L 16
 #ifndef BK_TU
 #define BK_TU 0
 #endif
@@ -4298,7 +4299,9 @@ __device__ __forceinline__ double tt_val_ld(const MctsArgs& a, const double* p) 
 }
 
 // lane / nl: the lanes sharing the search (the cooperative kernels: 0..63 of 64), which
-// split the agent row copies
+// split the agent row copies.  MT = false (k_mcts_coop_l): the search has no rollout
+// stream, a.mt is null
+template <bool MT = true>
 __device__ __forceinline__ void mc_start_game(const MctsArgs& a, Mc& m, McLane* L, int32_t g, const uint64_t* htab,
                                               int lane = 0, int nl = 1) {
     m.game = g;
@@ -4322,7 +4325,7 @@ __device__ __forceinline__ void mc_start_game(const MctsArgs& a, Mc& m, McLane* 
     }
     m.root_player = a.players[g] & 3;
     m.root_cp = a.roots[g].current_player & 3;
-    m.mt_pos = a.mt[(size_t)g * (FM_N + 1) + FM_N];
+    if constexpr (MT) m.mt_pos = a.mt[(size_t)g * (FM_N + 1) + FM_N];
     m.t0 = wall_clock64();
     if (a.cfg.resume) {  // a chunked search: carry on where the previous launch stopped
         const bk_mcts_out o = a.out[g];
@@ -4374,6 +4377,7 @@ __device__ __forceinline__ uint64_t mc_done_word(const bk_mcts_out& o) {
            ((uint64_t)(o.status & 0x7Fu) << 56) | (1ull << 63);
 }
 
+template <bool MT = true>
 __device__ __forceinline__ void mc_finish_game(const MctsArgs& a, Mc& m, int lane = 0, int nl = 1) {
     const int32_t g = m.game;
     const bk_mcts_node* pool = a.nodes + (size_t)g * a.cfg.node_cap;
@@ -4413,7 +4417,7 @@ __device__ __forceinline__ void mc_finish_game(const MctsArgs& a, Mc& m, int lan
         }
         if (a.cfg.use_tt) sys_st(a.tt_count + m.row, (int32_t)m.tt_cnt);
     } else {
-        a.mt[(size_t)g * (FM_N + 1) + FM_N] = m.mt_pos;
+        if constexpr (MT) a.mt[(size_t)g * (FM_N + 1) + FM_N] = m.mt_pos;
         if (a.cfg.use_tt) a.tt_count[g] = m.tt_cnt;
     }
     if (a.done) {  // after every store above (and the TT's) has completed: the wave's vmcnt
@@ -4494,19 +4498,26 @@ __device__ __forceinline__ void mc_sim_terminal(const MctsArgs& a, Mc& m, McLane
 // two dependent loads per child (a fully expanded root has hundreds of children, and a
 // lane's child block is not cache-resident).  Same operations, same order: the argmax is
 // the reference's.
+// BIAS (k_mcts_coop_l with progressive bias): ucb1_value's third term, bias_w *
+// (prior_bias / (1.0 + visits)), added after exploit + explore; pb = the children's
+// prior_bias entries (a side array indexed as the node pool is).
 #define MC_UCB_BATCH 16
-__device__ __forceinline__ int mc_ucb_best(const bk_mcts_node* cb, int n, double lg, double c_explore) {
+template <bool BIAS = false>
+__device__ __forceinline__ int mc_ucb_best(const bk_mcts_node* cb, int n, double lg, double c_explore,
+                                           const double* pb = nullptr, double bias_w = 0.0) {
     int best = 0;
     double bv = 0.0;
 #pragma unroll 1
     for (int k0 = 0; k0 < n; k0 += MC_UCB_BATCH) {
         double tot[MC_UCB_BATCH];
         uint32_t vis[MC_UCB_BATCH];
+        double pri[BIAS ? MC_UCB_BATCH : 1];
 #pragma unroll
         for (int j = 0; j < MC_UCB_BATCH; ++j) {
             const int k = k0 + j < n ? k0 + j : n - 1;  // in bounds; unused past n
             tot[j] = cb[k].total;
             vis[j] = cb[k].visits;
+            if constexpr (BIAS) pri[j] = pb[k];
         }
 #pragma unroll
         for (int j = 0; j < MC_UCB_BATCH; ++j) {
@@ -4519,6 +4530,7 @@ __device__ __forceinline__ int mc_ucb_best(const bk_mcts_node* cb, int n, double
                     const double exploit = tot[j] / vd;
                     const double explore = c_explore * __builtin_sqrt(lg / vd);
                     v = exploit + explore;
+                    if constexpr (BIAS) v = v + bias_w * (pri[j] / (1.0 + vd));
                 }
                 if (k0 + j == 0 || v > bv) { bv = v; best = k0 + j; }
             }
@@ -4530,7 +4542,9 @@ __device__ __forceinline__ int mc_ucb_best(const bk_mcts_node* cb, int n, double
 // selection (mcts_agent.py:384-406, UCB1 :68-111) from the root; leaves m.node at the
 // node to expand or simulate, m.depth / path / m.hash for it.  Returns true when that
 // node is evaluated terminal (no untried move, no child).
-__device__ __forceinline__ bool mc_select(const MctsArgs& a, Mc& m, McLane* L, const uint64_t* Z) {
+template <bool BIAS = false>
+__device__ __forceinline__ bool mc_select(const MctsArgs& a, Mc& m, McLane* L, const uint64_t* Z,
+                                          const double* prior = nullptr, double bias_w = 0.0) {
     const bk_mcts_node* pool = a.nodes + (size_t)m.game * a.cfg.node_cap;
     int u = 0, depth = 0;
     uint64_t h = a.root_hash[m.game];
@@ -4546,7 +4560,8 @@ __device__ __forceinline__ bool mc_select(const MctsArgs& a, Mc& m, McLane* L, c
         }
         if (depth >= BK_MCTS_MAX_DEPTH) { m.status |= BK_MCTS_EPATH; break; }
         const double lg = a.log_table[nd.visits];
-        const int best = nd.child0 + mc_ucb_best(pool + nd.child0, (int)nd.n_exp, lg, a.cfg.exploration);
+        const int best = nd.child0 + mc_ucb_best<BIAS>(pool + nd.child0, (int)nd.n_exp, lg, a.cfg.exploration,
+                                                       BIAS ? prior + nd.child0 : nullptr, bias_w);
         int gs, ar, ac;
         mc_move_split(pool[best].move, gs, ar, ac);
         h = mc_hash_step(Z, h, (m.root_player + depth) & 3, (m.root_cp + depth) & 3, gs, ar, ac);
@@ -5436,8 +5451,15 @@ __device__ __forceinline__ bool coop_walk(int gs, uint32_t kk, const uint2* rows
 
 static_assert(COOP_CUM_DWORD + 4 * BK_NUM_ORIENTS <= COOP_AREA, "the move list and sums fit a wave's area");
 
-template <bool HEUR>
-__device__ __forceinline__ void mcts_coop_body(const MctsArgs& a) {
+// LEAF (k_mcts_coop_l): the learned evaluator's value of the new node's board replaces the
+// rollout (mcts_agent.py:408-451 with leaf_evaluation_enabled), so the search is the tree
+// part plus one evaluation per simulation; `leaf` (LeafEval below) builds the four feature
+// rows of the board in the slab / table A and runs the pairwise chain.  With a
+// progressive-bias weight, every expansion also sets prior_bias(child) = V(child, mover) -
+// V(parent, mover) (:453-468) in the side array leaf.la.prior, which selection reads.
+struct NoLeaf {};
+template <bool HEUR, bool LEAF = false, typename Leaf = NoLeaf>
+__device__ __forceinline__ void mcts_coop_body(const MctsArgs& a, const Leaf& leaf = Leaf()) {
     constexpr int BLK = COOP_WAVES * WAVE;
     constexpr int HS_WORDS = HEUR ? (int)(sizeof(HeurShared) + 7) / 4 : 0;
     __shared__ __attribute__((aligned(16))) uint32_t lds[COOP_AREA * COOP_WAVES + 2 * BK_CELLS + HS_WORDS];
@@ -5451,7 +5473,7 @@ __device__ __forceinline__ void mcts_coop_body(const MctsArgs& a) {
     // so no launch leaves anything in it for the next -- and the mover's table is then
     // used in place (no LDS-DMA stage, no write-back).  (k_mcts_coop keeps it in HBM: the
     // 4.9 KB per wave would cost it a block per CU.)
-    constexpr bool ML_LDS = HEUR;
+    constexpr bool ML_LDS = HEUR || LEAF;
     __shared__ __attribute__((aligned(16))) McLane coop_ml[ML_LDS ? COOP_WAVES : 1];
     const bool coop_walk_on = a.coop_walk != 0;
     // the wave index is uniform (readfirstlane): the wave's LDS area, slab and McLane
@@ -5472,6 +5494,10 @@ __device__ __forceinline__ void mcts_coop_body(const MctsArgs& a) {
     m.game = -1;
     m.mode = MC_SELECT;
     int root_mc = 0;  // Board.move_count of the search's root
+    [[maybe_unused]] int32_t bias_upd = 0;     // LEAF: progressive-bias updates of the search
+    [[maybe_unused]] bool bias_on = false;     // LEAF: (uniform, constant for the launch)
+    [[maybe_unused]] double* prior = nullptr;  // LEAF: the search's prior_bias entries, by node
+    if constexpr (LEAF) bias_on = leaf.la.bias_w != 0.0;
     // section timers (-DBK_SECTION_PROF): 0 tree, 1 derive + rows, 2 lane orientations +
     // scan, 3 draw + pick, 4 locate / heuristic walk, 5 frontier ops + place + expansion
     SECT_DECL
@@ -5496,15 +5522,42 @@ __device__ __forceinline__ void mcts_coop_body(const MctsArgs& a) {
                 uint32_t twice = 0;
                 if (lane == 0) twice = mc_mark_started(a, next, (uint32_t)next) ? 1u : 0u;
                 twice = __shfl(twice, 0);
-                mc_start_game(a, m, L, next, htab, lane, WAVE);
+                mc_start_game<!LEAF>(a, m, L, next, htab, lane, WAVE);
                 if (twice) m.status |= BK_MCTS_EINTERNAL;
                 root_mc = (int)a.roots[next].move_count;  // (constant for the search)
+                if constexpr (LEAF) {
+                    bias_upd = a.cfg.resume ? leaf.la.bias_updates[next] : 0;
+                    if (bias_on) prior = leaf.la.prior + (size_t)next * a.cfg.node_cap;
+                }
             }
             const bool timed_out = a.cfg.time_limit_us > 0 && wall_clock64() - m.t0 >= a.limit_ticks;
             const bool chunk_end = a.cfg.iter_stop > 0 && m.it >= a.cfg.iter_stop;
-            if (m.it >= a.cfg.iterations || chunk_end || timed_out || MC_FATAL(m.status)) { mc_finish_game(a, m, lane, WAVE); continue; }
+            if (m.it >= a.cfg.iterations || chunk_end || timed_out || MC_FATAL(m.status)) {
+                if constexpr (LEAF) leaf.la.bias_updates[m.game] = bias_upd;
+                mc_finish_game<!LEAF>(a, m, lane, WAVE);
+                continue;
+            }
             const uint64_t* Z = a.zobrist + (size_t)a.zidx[m.game] * MC_ZOB;
-            if (mc_select(a, m, L, Z)) { mc_sim_terminal(a, m, L); continue; }
+            if constexpr (LEAF) {
+                const bool term = bias_on ? mc_select<true>(a, m, L, Z, prior, leaf.la.bias_w) : mc_select(a, m, L, Z);
+                if (term) {  // _simulation of a terminal node: its own board's value, unless the TT has it
+                    double reward = 0.0;
+                    const bool hit = a.cfg.use_tt && mc_tt_lookup(a, m, reward);
+                    if (!hit) {
+                        mc_replay(a, m, slab, L, htab, lk);
+                        if (MC_FATAL(m.status)) continue;
+                        if (leaf.features(slab, L->A.s, m, root_mc + m.depth, my, coop_rank[wv], lane)) {
+                            m.status |= BK_MCTS_EINTERNAL;
+                            continue;
+                        }
+                        reward = leaf.value((m.root_player + m.depth) & 3, my, lane);
+                    }
+                    mc_complete(a, m, L, reward, hit);
+                    continue;
+                }
+            } else {
+                if (mc_select(a, m, L, Z)) { mc_sim_terminal(a, m, L); continue; }
+            }
             if (MC_FATAL(m.status)) continue;
             mc_replay(a, m, slab, L, htab, lk);
             m.mode = MC_EXPAND;
@@ -5516,7 +5569,18 @@ __device__ __forceinline__ void mcts_coop_body(const MctsArgs& a) {
             break;
         }
         // ---- one movegen, split over the lanes
-        const int p = m.mode == MC_EXPAND ? ((m.root_player + m.depth) & 3) : m.cur;
+        const int p = LEAF || m.mode == MC_EXPAND ? ((m.root_player + m.depth) & 3) : m.cur;  // (LEAF: no rollout plies)
+        [[maybe_unused]] double v_node = 0.0;  // LEAF with bias: V(node, its mover), before the placement
+        if constexpr (LEAF) {
+            if (bias_on) {
+                if (leaf.features(slab, L->A.s, m, root_mc + m.depth, my, coop_rank[wv], lane)) {
+                    m.status |= BK_MCTS_EINTERNAL;
+                    m.mode = MC_SELECT;
+                    continue;
+                }
+                v_node = leaf.value(p, my, lane);
+            }
+        }
         const uint32_t tmask = L->A.s.mask[p];  // (loaded with the slab rows)
         Planes P;
         {
@@ -5561,7 +5625,7 @@ __device__ __forceinline__ void mcts_coop_body(const MctsArgs& a) {
         SECT(2);
         bk_mcts_node* pool = a.nodes + (size_t)m.game * a.cfg.node_cap;
         uint32_t k = 0;
-        if (m.mode == MC_EXPAND) {
+        if (LEAF || m.mode == MC_EXPAND) {
             bk_mcts_node* nd = pool + m.node;
             uint32_t n_legal = nd->n_legal, n_exp = nd->n_exp;
             if (!(nd->flags & BK_MCTS_NODE_EVALUATED)) {  // MCTSNode._initialize_untried_moves
@@ -5576,7 +5640,21 @@ __device__ __forceinline__ void mcts_coop_body(const MctsArgs& a) {
                 continue;
             }
             if (n_legal == n_exp) {  // no legal move: terminal leaf
-                mc_sim_terminal(a, m, L);
+                if constexpr (LEAF) {
+                    double reward = 0.0;
+                    const bool hit = a.cfg.use_tt && mc_tt_lookup(a, m, reward);
+                    if (!hit) {
+                        if (!bias_on && leaf.features(slab, L->A.s, m, root_mc + m.depth, my, coop_rank[wv], lane)) {
+                            m.status |= BK_MCTS_EINTERNAL;
+                            m.mode = MC_SELECT;
+                            continue;
+                        }
+                        reward = bias_on ? v_node : leaf.value(p, my, lane);
+                    }
+                    mc_complete(a, m, L, reward, hit);
+                } else {
+                    mc_sim_terminal(a, m, L);
+                }
                 continue;
             }
             k = n_legal - n_exp - 1u;  // untried_moves.pop(): the last list entry
@@ -5657,13 +5735,22 @@ __device__ __forceinline__ void mcts_coop_body(const MctsArgs& a) {
         piece_cells(gs, ar, ac, pm, cells);
         const uint64_t real = frontier_ops(rows_lds, slab, p, (m.first >> p) & 1u, gs, ar, ac, pm);
         SECT(8);
-        const bool expand = m.mode == MC_EXPAND;
+        const bool expand = LEAF || m.mode == MC_EXPAND;
         uint32_t c = 0;
         bool ok = true;
         if (expand) {
             bk_mcts_node* nd = pool + m.node;
+            [[maybe_unused]] const int32_t ob = nd->child0;
+            [[maybe_unused]] const uint32_t ne0 = nd->n_exp;
             const int32_t cs = mc_child_slot(pool, nd, m, a.cfg.node_cap);
             if (cs < 0) { m.status |= BK_MCTS_EPOOL; m.mode = MC_SELECT; continue; }
+            if constexpr (LEAF) {  // a child block that moved takes its prior_bias entries along
+                const int32_t nb = nd->child0;
+                if (bias_on && nb != ob) {
+#pragma unroll 1
+                    for (uint32_t k2 = 0; k2 < ne0; ++k2) prior[nb + k2] = prior[ob + k2];
+                }
+            }
             c = (uint32_t)cs;
             nd->n_exp = (uint16_t)(nd->n_exp + 1u);
             bk_mcts_node ch;
@@ -5700,6 +5787,23 @@ __device__ __forceinline__ void mcts_coop_body(const MctsArgs& a) {
             L->path[++m.depth] = (int32_t)c;
             m.node = (int32_t)c;
             double reward = 0.0;
+            if constexpr (LEAF) {
+                const bool hit = a.cfg.use_tt && mc_tt_lookup(a, m, reward);
+                if (bias_on || !hit) {  // one feature pass serves the bias and the leaf value
+                    if (leaf.features(slab, L->A.s, m, root_mc + m.depth, my, coop_rank[wv], lane)) {
+                        m.status |= BK_MCTS_EINTERNAL;
+                        m.mode = MC_SELECT;
+                        continue;
+                    }
+                }
+                if (bias_on) {  // _update_progressive_bias(parent, child), for the parent's mover p
+                    prior[c] = leaf.value(p, my, lane) - v_node;
+                    bias_upd++;
+                }
+                if (!hit) reward = leaf.value((m.root_player + m.depth) & 3, my, lane);
+                mc_complete(a, m, L, reward, hit);
+                continue;
+            }
             if (a.cfg.use_tt && mc_tt_lookup(a, m, reward)) {
                 mc_complete(a, m, L, reward, true);
                 continue;
@@ -6143,7 +6247,7 @@ struct WinprobArgs {
 static_assert(sizeof(bk_snapshot_rec) == 80 && sizeof(bk_snapshot_rec) % 8 == 0, "the record is copied out as dwords");
 static_assert(BK_SNAPSHOT_COLUMNS <= WAVE, "one lane per column");
 
-#if BK_DEF(BK_U_SNAPSHOT)
+#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L)
 // O_i (distinct orientations), S_i (cells) and the pieces of each size, from the orientation table
 struct SnapTab {
     uint8_t orients[BK_PIECES], size[BK_PIECES];
@@ -6162,6 +6266,134 @@ constexpr SnapTab snap_tab() {
 }
 __constant__ SnapTab kSnapTab = snap_tab();
 
+// The per-player routines of a snapshot row, shared by the four-wave kernels below (wave p
+// for player p) and the in-search evaluation of k_mcts_coop_l (one wave, p = 0..3 in turn).
+//
+// A player's frontier cells as row masks (atomicOr into fr[20], LDS) from a table's keys;
+// returns the number of active keys.  bad: the mask or an active slot is out of range.
+// (snap_rows keeps an inline copy of this loop for its global table: change both.)
+__device__ __forceinline__ uint32_t snap_frontier_keys(const int16_t* key, int tmask, int lane, uint32_t* fr,
+                                                       bool& bad_table) {
+    bad_table = tmask >= BK_FSET_SLOTS;
+    tmask = tmask < BK_FSET_SLOTS ? tmask : BK_FSET_SLOTS - 1;
+    uint32_t fsize = 0;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const int sl = lane + WAVE * h;
+        const int k = sl <= tmask ? (int)key[sl] : -1;
+        const bool is_key = k >= 0 && k < BK_CELLS;
+        bad_table = bad_table || k >= BK_CELLS || k < -2;  // (-1 unused, -2 dummy)
+        if (is_key) atomicOr(&fr[k / 20], 1u << (k % 20));
+        fsize += (uint32_t)__popcll(__ballot(is_key));
+    }
+    return fsize;
+}
+
+// The player's row scans, row R in lane R (the other lanes hold empty rows)
+struct SnapScans { uint32_t cdist, adj, own_cells, occ_cells; };
+__device__ __forceinline__ SnapScans snap_scans(uint32_t r_own, uint32_t r_occ, int R, int lane) {
+    SnapScans o;
+    uint32_t cdist = 9;  // compute_center_proximity: 9 unless a cell is nearer
+    if (r_own) {
+        const uint32_t lo = r_own & 0x3FFu, hi = r_own >> 10;
+        uint32_t dc = 9;
+        if (lo) dc = 9u - (31u - (uint32_t)__builtin_clz(lo));
+        if (hi) { const uint32_t t = (uint32_t)__builtin_ctz(hi); dc = t < dc ? t : dc; }
+        cdist = (uint32_t)(R <= 9 ? 9 - R : R - 10) + dc;
+        cdist = cdist > 9u ? 9u : cdist;
+    }
+#pragma unroll
+    for (int o2 = WAVE / 2; o2; o2 >>= 1) {
+        const uint32_t t = (uint32_t)__shfl_xor((int)cdist, o2);
+        cdist = t < cdist ? t : cdist;
+    }
+    o.cdist = cdist;
+    // compute_opponent_adjacency: own cells with another player's cell orthogonally beside them
+    const uint32_t r_opp = r_occ & ~r_own;
+    const uint32_t opp_up = __shfl_up(r_opp, 1), opp_dn = __shfl_down(r_opp, 1);
+    const uint32_t near_opp = (r_opp << 1) | (r_opp >> 1) | (lane >= 1 ? opp_up : 0u) | (lane < WAVE - 1 ? opp_dn : 0u);
+    o.adj = tel_wave_sum((uint32_t)__builtin_popcount(r_own & near_opp), lane);
+    o.own_cells = tel_wave_sum((uint32_t)__builtin_popcount(r_own), lane);
+    o.occ_cells = tel_wave_sum((uint32_t)__builtin_popcount(r_occ), lane);
+    return o;
+}
+
+// compute_dead_zones: empty cells whose 4-connected component holds no frontier key of any
+// player = the empty cells a fill from all the keys does not reach (a stale key on an
+// occupied cell seeds nothing).  r_allfr: every player's frontier cells of row `lane`.
+__device__ __forceinline__ uint32_t snap_dead_zones(uint32_t r_allfr, uint32_t r_occ, bool rl, int lane) {
+    const uint32_t r_empty = rl ? (~r_occ & ROWMASK) : 0u;
+    const uint32_t r_live = tel_flood<1>(r_allfr, r_empty, lane);
+    return tel_wave_sum((uint32_t)__builtin_popcount(r_empty & ~r_live), lane);
+}
+
+// The scalars of one player's row, and the row itself from them and the per-piece terms
+// norm[i] = P_i / O_i, wt[i] = norm[i] * S_i (LDS, complete).  compute_player_mobility_metrics'
+// sums, pieces in ascending id, used pieces skipped: lane 0 total_norm, lanes 1..5 the size
+// buckets, lane 6 total_weighted; lane 0 writes the other columns.
+struct SnapScalars {
+    uint32_t used, fsize, cdist, adj, dead, mob, opp_moves, used_count, ply, occ_cells, own_cells;
+    int corner_diff;
+    int32_t turn, max_turns;
+};
+__device__ __forceinline__ void snap_piece_terms(uint32_t P, int lane, double* norm, double* wt) {
+    const double nrm = __ddiv_rn((double)P, (double)kSnapTab.orients[lane]);  // count / n_orient
+    norm[lane] = nrm;
+    wt[lane] = __dmul_rn(nrm, (double)kSnapTab.size[lane]);                   // normalized * size
+}
+__device__ __forceinline__ void snap_row_fill(double* f, int lane, const SnapScalars& v, const double* norm,
+                                              const double* wt) {
+    double acc = 0.0;
+#pragma unroll 1
+    for (int i = 0; i < BK_PIECES; ++i) {
+        const uint32_t S = kSnapTab.size[i];
+        const double x = lane == 0 ? norm[i] : wt[i];
+        const bool take = !((v.used >> i) & 1u) && (lane == 0 || lane == 6 || (uint32_t)lane == S);
+        acc = take ? __dadd_rn(acc, x) : acc;
+    }
+    if (lane == 0) f[7] = acc;
+    if (lane >= 1 && lane <= 5) f[8 + lane] = acc;
+    if (lane == 6) {
+        f[8] = acc;
+        f[15] = __dadd_rn((double)v.fsize, acc);  // frontier_size + totalCellWeighted
+    }
+    if (lane == 0) {
+        const uint32_t avail = ~v.used & 0x1FFFFFu;
+        const double cells = (double)BK_CELLS;
+        const double span = (double)(v.max_turns > 1 ? v.max_turns : 1);  // max(1, max_turns)
+        uint32_t squares = 0;
+#pragma unroll
+        for (int b = 1; b <= 5; ++b) {
+            const uint32_t nb = (uint32_t)__builtin_popcount(avail & kSnapTab.of_size[b]);
+            f[18 + b] = (double)nb;  // remaining_size_b_count
+            squares += (uint32_t)b * nb;
+        }
+        f[0] = (double)v.fsize;
+        f[1] = (double)v.corner_diff;
+        f[2] = (double)v.cdist;
+        f[3] = (double)v.adj;
+        f[4] = (double)v.dead;
+        f[5] = __ddiv_rn((double)v.dead, cells);
+        f[6] = (double)v.mob;
+        f[14] = (double)v.opp_moves;
+        f[16] = (double)v.used_count;
+        f[17] = (double)(BK_PIECES - v.used_count);
+        f[18] = (double)squares;  // total squares - used squares
+        f[24] = (double)((avail >> 16) & 1u);
+        f[25] = (double)((avail >> 18) & 1u);
+        f[26] = (double)((avail >> 19) & 1u);
+        f[27] = (double)v.ply;
+        f[28] = (double)v.turn;
+        f[29] = __ddiv_rn((double)v.occ_cells, cells);
+        f[30] = __ddiv_rn((double)v.used_count, 21.0);
+        f[31] = __ddiv_rn((double)v.turn, span);
+        f[32] = __ddiv_rn((double)v.ply, span);
+        f[33] = __ddiv_rn((double)v.own_cells, cells);
+    }
+}
+#endif  // the snapshot routines
+
+#if BK_DEF(BK_U_SNAPSHOT)
 // The four rows of one board (the block's), left in s_feat.  EVAL = false is k_snapshot: the
 // records and rows also go to global memory and a call without a.feat stops after the records.
 // EVAL = true is k_winprob: nothing is written to global memory, every wave builds its row
@@ -6201,7 +6433,10 @@ __device__ __forceinline__ uint32_t snap_rows(const SnapArgs& a, double (&s_feat
     }
     if (lane == 0 && ((s->planes[p][BK_MASK_WORDS - 1] >> (BK_CELLS - 64 * (BK_MASK_WORDS - 1))) || (s->used[p] >> BK_PIECES)))
         atomicOr(&s_status, BK_SNAP_ST_STATE);
-    // the player's frontier cells as row masks, from the table's keys
+    // the player's frontier cells as row masks, from the table's keys.  This is
+    // snap_frontier_keys' text, kept inline (calling the shared copy changes k_snapshot's
+    // address arithmetic for the global table): the two must state the same key, status and
+    // bad_table rule -- change them together.
     int tmask = (int)fs->mask[p];
     bool bad_table = tmask >= BK_FSET_SLOTS;
     tmask = tmask < BK_FSET_SLOTS ? tmask : BK_FSET_SLOTS - 1;
@@ -6247,35 +6482,11 @@ __device__ __forceinline__ uint32_t snap_rows(const SnapArgs& a, double (&s_feat
     const bool rl = lane < 20;
     const int R = rl ? lane : 0;
     const uint32_t r_own = rl ? s_own[p][R] : 0u, r_occ = rl ? s_occ[R] : 0u;
-    uint32_t cdist = 9;  // compute_center_proximity: 9 unless a cell is nearer
-    if (r_own) {
-        const uint32_t lo = r_own & 0x3FFu, hi = r_own >> 10;
-        uint32_t dc = 9;
-        if (lo) dc = 9u - (31u - (uint32_t)__builtin_clz(lo));
-        if (hi) { const uint32_t t = (uint32_t)__builtin_ctz(hi); dc = t < dc ? t : dc; }
-        cdist = (uint32_t)(R <= 9 ? 9 - R : R - 10) + dc;
-        cdist = cdist > 9u ? 9u : cdist;
-    }
-#pragma unroll
-    for (int o = WAVE / 2; o; o >>= 1) {
-        const uint32_t t = (uint32_t)__shfl_xor((int)cdist, o);
-        cdist = t < cdist ? t : cdist;
-    }
-    // compute_opponent_adjacency: own cells with another player's cell orthogonally beside them
-    const uint32_t r_opp = r_occ & ~r_own;
-    const uint32_t opp_up = __shfl_up(r_opp, 1), opp_dn = __shfl_down(r_opp, 1);
-    const uint32_t near_opp = (r_opp << 1) | (r_opp >> 1) | (lane >= 1 ? opp_up : 0u) | (lane < WAVE - 1 ? opp_dn : 0u);
-    const uint32_t adj = tel_wave_sum((uint32_t)__builtin_popcount(r_own & near_opp), lane);
-    const uint32_t own_cells = tel_wave_sum((uint32_t)__builtin_popcount(r_own), lane);
-    const uint32_t occ_cells = tel_wave_sum((uint32_t)__builtin_popcount(r_occ), lane);
-    if (p == 0) {
-        // compute_dead_zones: empty cells whose 4-connected component holds no frontier key of any
-        // player = the empty cells a fill from all the keys does not reach (a stale key on an
-        // occupied cell seeds nothing)
+    const SnapScans sc = snap_scans(r_own, r_occ, R, lane);
+    const uint32_t cdist = sc.cdist, adj = sc.adj, own_cells = sc.own_cells, occ_cells = sc.occ_cells;
+    if (p == 0) {  // the board-wide dead zones, from every player's keys
         const uint32_t r_allfr = rl ? (s_fr[0][R] | s_fr[1][R] | s_fr[2][R] | s_fr[3][R]) : 0u;
-        const uint32_t r_empty = rl ? (~r_occ & ROWMASK) : 0u;
-        const uint32_t r_live = tel_flood<1>(r_allfr, r_empty, lane);
-        const uint32_t dead = tel_wave_sum((uint32_t)__builtin_popcount(r_empty & ~r_live), lane);
+        const uint32_t dead = snap_dead_zones(r_allfr, r_occ, rl, lane);
         if (lane == 0) s_dead = dead;
     }
     if (lane == 0) s_mob[p] = mob;
@@ -6296,9 +6507,7 @@ __device__ __forceinline__ uint32_t snap_rows(const SnapArgs& a, double (&s_feat
     if (lane < BK_PIECES) {
         const uint32_t P = s_pc[p][lane];
         if (!EVAL) rec.piece_count[lane] = (uint16_t)P;
-        const double nrm = __ddiv_rn((double)P, (double)kSnapTab.orients[lane]);  // count / n_orient
-        s_norm[p][lane] = nrm;
-        s_wt[p][lane] = __dmul_rn(nrm, (double)kSnapTab.size[lane]);              // normalized * size
+        snap_piece_terms(P, lane, s_norm[p], s_wt[p]);
     }
     if (!EVAL && lane == 0) {
         rec.mobility = mob;
@@ -6325,56 +6534,9 @@ __device__ __forceinline__ uint32_t snap_rows(const SnapArgs& a, double (&s_feat
         }
         if (a.feat == nullptr) return status;  // (uniform)
     }
-    // compute_player_mobility_metrics' sums, pieces in ascending id, used pieces skipped: lane 0
-    // total_norm, lanes 1..5 the size buckets, lane 6 total_weighted
-    double acc = 0.0;
-#pragma unroll 1
-    for (int i = 0; i < BK_PIECES; ++i) {
-        const uint32_t S = kSnapTab.size[i];
-        const double v = lane == 0 ? s_norm[p][i] : s_wt[p][i];
-        const bool take = !((used >> i) & 1u) && (lane == 0 || lane == 6 || (uint32_t)lane == S);
-        acc = take ? __dadd_rn(acc, v) : acc;
-    }
     double* f = s_feat[p];
-    if (lane == 0) f[7] = acc;
-    if (lane >= 1 && lane <= 5) f[8 + lane] = acc;
-    if (lane == 6) {
-        f[8] = acc;
-        f[15] = __dadd_rn((double)fsize, acc);  // frontier_size + totalCellWeighted
-    }
-    if (lane == 0) {
-        const uint32_t avail = ~used & 0x1FFFFFu;
-        const double cells = (double)BK_CELLS;
-        const double span = (double)(a.max_turns > 1 ? a.max_turns : 1);  // max(1, max_turns)
-        uint32_t squares = 0;
-#pragma unroll
-        for (int b = 1; b <= 5; ++b) {
-            const uint32_t nb = (uint32_t)__builtin_popcount(avail & kSnapTab.of_size[b]);
-            f[18 + b] = (double)nb;  // remaining_size_b_count
-            squares += (uint32_t)b * nb;
-        }
-        f[0] = (double)fsize;
-        f[1] = (double)corner_diff;
-        f[2] = (double)cdist;
-        f[3] = (double)adj;
-        f[4] = (double)dead;
-        f[5] = __ddiv_rn((double)dead, cells);
-        f[6] = (double)mob;
-        f[14] = (double)opp_moves;
-        f[16] = (double)used_count;
-        f[17] = (double)(BK_PIECES - used_count);
-        f[18] = (double)squares;  // total squares - used squares
-        f[24] = (double)((avail >> 16) & 1u);
-        f[25] = (double)((avail >> 18) & 1u);
-        f[26] = (double)((avail >> 19) & 1u);
-        f[27] = (double)ply;
-        f[28] = (double)turn;
-        f[29] = __ddiv_rn((double)occ_cells, cells);
-        f[30] = __ddiv_rn((double)used_count, 21.0);
-        f[31] = __ddiv_rn((double)turn, span);
-        f[32] = __ddiv_rn((double)ply, span);
-        f[33] = __ddiv_rn((double)own_cells, cells);
-    }
+    snap_row_fill(f, lane, SnapScalars{used, fsize, cdist, adj, dead, mob, opp_moves, used_count, ply, occ_cells,
+                                       own_cells, corner_diff, turn, a.max_turns}, s_norm[p], s_wt[p]);
     tel_wave_sync();
     if (!EVAL && lane < BK_SNAPSHOT_COLUMNS)
         a.feat[((size_t)board * 4 + (size_t)p) * BK_SNAPSHOT_COLUMNS + (size_t)lane] = f[lane];
@@ -6396,7 +6558,35 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
 // rounded exp wherever a host libm's is; the device library's (within 1 ulp) left 1 prob of
 // 172 on the edge boards 2 ulp from CPython's.  It overflows to +inf (s = 0) and underflows
 // to 0 (s = 1) for very large |t|.
+#endif  // BK_DEF(BK_U_SNAPSHOT)
+#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L)
 #include "exp_cr.h"
+// The chain's two steps for player p, shared with k_mcts_coop_l: lane k's three terms into
+// u[3][columns] (LDS), then -- after the wave's sync -- lane j < 3 sums opponent j's terms
+// (t, the pair logit) and returns the sigmoid.
+__device__ __forceinline__ void winprob_terms(const bk_winprob_model& m, int p, int lane,
+                                              const double (*feat)[BK_SNAPSHOT_COLUMNS],
+                                              double (*u)[BK_SNAPSHOT_COLUMNS]) {
+#pragma clang fp contract(off)
+    const double fp = feat[p][lane];
+    const double mean = m.mean[lane], scale = m.scale[lane], coef = m.coef[lane];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int q = j + (j >= p ? 1 : 0);
+        const double x = __dsub_rn(fp, feat[q][lane]);
+        u[j][lane] = __dmul_rn(__ddiv_rn(__dsub_rn(x, mean), scale), coef);
+    }
+}
+__device__ __forceinline__ double winprob_sigmoid(const bk_winprob_model& m, const double* uj, double& t) {
+#pragma clang fp contract(off)
+    t = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < BK_SNAPSHOT_COLUMNS; ++k) t = __dadd_rn(t, uj[k]);
+    t = __dadd_rn(t, m.intercept);
+    return __ddiv_rn(1.0, __dadd_rn(1.0, bk_exp_cr(-t)));
+}
+#endif
+#if BK_DEF(BK_U_SNAPSHOT)
 __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_winprob(WinprobArgs a) {
 #pragma clang fp contract(off)
     __shared__ __attribute__((aligned(8))) double s_feat[SNAP_WAVES][BK_SNAPSHOT_COLUMNS];
@@ -6406,24 +6596,12 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_winprob(WinprobArgs a) {
     const size_t board = blockIdx.x;  // the grid is exactly n blocks
     const uint32_t status = snap_rows<true>(a.s, s_feat);
     __syncthreads();  // the four rows are complete
-    if (lane < BK_SNAPSHOT_COLUMNS) {
-        const double fp = s_feat[p][lane];
-        const double mean = a.m.mean[lane], scale = a.m.scale[lane], coef = a.m.coef[lane];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int q = j + (j >= p ? 1 : 0);
-            const double x = __dsub_rn(fp, s_feat[q][lane]);
-            s_u[p][j][lane] = __dmul_rn(__ddiv_rn(__dsub_rn(x, mean), scale), coef);
-        }
-    }
+    if (lane < BK_SNAPSHOT_COLUMNS) winprob_terms(a.m, p, lane, s_feat, s_u[p]);
     tel_wave_sync();
     double sg = 0.0;
     if (lane < 3) {
-        double t = 0.0;
-#pragma unroll 1
-        for (int k = 0; k < BK_SNAPSHOT_COLUMNS; ++k) t = __dadd_rn(t, s_u[p][lane][k]);
-        t = __dadd_rn(t, a.m.intercept);
-        sg = __ddiv_rn(1.0, __dadd_rn(1.0, bk_exp_cr(-t)));
+        double t;
+        sg = winprob_sigmoid(a.m, s_u[p][lane], t);
         if (a.pair_logit != nullptr) a.pair_logit[(board * 4 + (size_t)p) * 3 + (size_t)lane] = t;
     }
     const double s1 = __shfl(sg, 1), s2 = __shfl(sg, 2);
@@ -6433,6 +6611,143 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_winprob(WinprobArgs a) {
 #else
 __global__ void k_snapshot(SnapArgs a);
 __global__ void k_winprob(WinprobArgs a);
+#endif
+
+// ------------------------------------------------------------------------------------
+// k_mcts_coop_l: MCTSAgent searches with learned leaf evaluation (bk_mcts_learned), whole
+// in one launch.  One wave per search, mcts_coop_body's tree part; where a rollout would
+// start, the wave evaluates the node's board with the learned evaluator instead -- the
+// arithmetic of k_winprob on the board it holds in LDS: the slab's planes, table A's
+// frontier keys, move_count = turn_index = the root's move_count + depth.  One wave builds
+// the four players' rows in turn with the routines k_snapshot's four waves use (one
+// rounding per reference operation, products through LDS before the ordered sums), then
+// runs the pairwise chain for the player asked for, so a value equals bk_winprob_eval's
+// for the same board bit for bit.  No rollout, no rollout policy, no MT stream.
+// LDS: the wave's area holds the {B, C} rows in its first 40 dwords per lane (as for the
+// movegen) and LeafScratch after them.
+// ------------------------------------------------------------------------------------
+struct LeafArgs {
+    bk_winprob_model m;     // by value in the kernel arguments
+    int32_t max_turns;
+    double bias_w;          // progressive_bias_weight, 0 = no progressive bias
+    double* prior;          // n x node_cap prior_bias entries (bias_w != 0)
+    int32_t* bias_updates;  // n: progressive-bias updates per search
+};
+
+#if BK_DEF(BK_U_COOP_L)
+struct LeafScratch {
+    double feat[4][BK_SNAPSHOT_COLUMNS];
+    double u[3][BK_SNAPSHOT_COLUMNS];
+    double norm[BK_PIECES], wt[BK_PIECES];
+    uint32_t fr[4][20], pc[4][BK_PIECES];
+    uint32_t mob[4], fsz[4], cdist[4], adj[4], own_cells[4];
+    uint32_t status;
+};
+static_assert(COOP_ML_DWORD * 4 + sizeof(LeafScratch) <= COOP_AREA * 4, "the evaluation's scratch fits a wave's area");
+
+struct LeafEval {
+    const LeafArgs& la;
+
+    // The four feature rows of the board in slab / T (used pieces and first-move flags from
+    // m) into the wave's scratch.  Returns the snapshot status bits (0 = a valid board).
+    __device__ __forceinline__ uint32_t features(const Slab& slab, const bk_fset& T, const Mc& m, int ply, uint32_t* my,
+                                                 int16_t* otab, int lane) const {
+#pragma clang fp contract(off)
+        LeafScratch& S = *reinterpret_cast<LeafScratch*>(my + COOP_ML_DWORD);
+        uint2* rows = reinterpret_cast<uint2*>(my) + lane;
+        tel_wave_sync();  // the placement's stores to the slab and the tables are visible
+        for (int i = lane; i < 4 * 20; i += WAVE) (&S.fr[0][0])[i] = 0u;
+        for (int i = lane; i < 4 * BK_PIECES; i += WAVE) (&S.pc[0][0])[i] = 0u;
+        if (lane == 0) S.status = 0u;
+        tel_wave_sync();
+        const bool rl = lane < 20;
+        const int R = rl ? lane : 0;
+        const uint32_t r_occ = rl ? slab.at(4, R) : 0u;
+        uint32_t occ_cells = 0, seen = 0, overlap = 0;
+#pragma unroll 1
+        for (int q = 0; q < 4; ++q) {
+            bool bad_table;
+            const uint32_t fsize = snap_frontier_keys(T.key[q], (int)T.mask[q], lane, S.fr[q], bad_table);
+            if (__ballot(bad_table) && lane == 0) atomicOr(&S.status, BK_SNAP_ST_TABLE);
+            {
+                uint32_t own[20], occ[20], B[20], C[20];
+#pragma unroll
+                for (int r = 0; r < 20; ++r) { own[r] = slab.at(q, r); occ[r] = slab.at(4, r); }
+                derive_rows(own, occ, (m.first >> q) & 1u, q, B, C);
+#pragma unroll
+                for (int r = 0; r < 20; ++r) rows[r * WAVE] = make_uint2(B[r], C[r]);
+            }
+            tel_wave_sync();
+            int og[2];
+            const uint32_t nlive = coop_live_orients(~m.used.get(q) & 0x1FFFFFu, lane, otab, og);
+            uint32_t mob;
+            {
+                uint32_t ok0[20], ok1[20], cnt[2];
+                coop_ok_counts(rows, og, nlive, ok0, ok1, cnt);
+                mob = coop_scan(cnt, lane).total;
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+                    if (og[h] >= 0 && cnt[h]) atomicAdd(&S.pc[q][(kInfo[og[h]] & 0xFFu) - 1u], cnt[h]);
+            }
+            const uint32_t r_own = rl ? slab.at(q, R) : 0u;
+            overlap |= r_own & seen;
+            seen |= r_own;
+            const SnapScans sc = snap_scans(r_own, r_occ, R, lane);
+            occ_cells = sc.occ_cells;
+            if (lane == 0) {
+                S.mob[q] = mob;
+                S.fsz[q] = fsize;
+                S.cdist[q] = sc.cdist;
+                S.adj[q] = sc.adj;
+                S.own_cells[q] = sc.own_cells;
+            }
+            tel_wave_sync();  // the next player reuses otab and the rows
+        }
+        if (__ballot(overlap != 0u || seen != r_occ) && lane == 0) atomicOr(&S.status, BK_SNAP_ST_STATE);
+        const uint32_t r_allfr = rl ? (S.fr[0][R] | S.fr[1][R] | S.fr[2][R] | S.fr[3][R]) : 0u;
+        const uint32_t dead = snap_dead_zones(r_allfr, r_occ, rl, lane);
+#pragma unroll 1
+        for (int q = 0; q < 4; ++q) {
+            if (lane < BK_PIECES) snap_piece_terms(S.pc[q][lane], lane, S.norm, S.wt);
+            tel_wave_sync();
+            uint32_t opp_moves = 0, opp_fr = 0;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                opp_moves += o == q ? 0u : S.mob[o];
+                opp_fr += o == q ? 0u : S.fsz[o];
+            }
+            const uint32_t used = m.used.get(q) & 0x1FFFFFu, fsize = S.fsz[q];
+            snap_row_fill(S.feat[q], lane, SnapScalars{used, fsize, S.cdist[q], S.adj[q], dead, S.mob[q], opp_moves,
+                                                       (uint32_t)__builtin_popcount(used), (uint32_t)ply, occ_cells,
+                                                       S.own_cells[q], (int)fsize - (int)opp_fr, (int32_t)ply,
+                                                       la.max_turns}, S.norm, S.wt);
+            tel_wave_sync();  // the row is complete; norm / wt are free for the next player
+        }
+        return S.status;
+    }
+
+    // Player p's win probability from the rows features() left (uniform over the wave)
+    __device__ __forceinline__ double value(int p, uint32_t* my, int lane) const {
+#pragma clang fp contract(off)
+        LeafScratch& S = *reinterpret_cast<LeafScratch*>(my + COOP_ML_DWORD);
+        if (lane < BK_SNAPSHOT_COLUMNS) winprob_terms(la.m, p, lane, S.feat, S.u);
+        tel_wave_sync();
+        double sg = 0.0;
+        if (lane < 3) {
+            double t;
+            sg = winprob_sigmoid(la.m, S.u[lane], t);
+        }
+        const double s0 = lane_bcast(sg, 0), s1 = lane_bcast(sg, 1), s2 = lane_bcast(sg, 2);
+        tel_wave_sync();  // u is free for the next call
+        return __ddiv_rn(__dadd_rn(__dadd_rn(s0, s1), s2), 3.0);
+    }
+};
+
+__global__ __launch_bounds__(COOP_WAVES * WAVE) void k_mcts_coop_l(MctsArgs a, LeafArgs la) {
+    mcts_coop_body<false, true>(a, LeafEval{la});
+}
+#else
+__global__ void k_mcts_coop_l(MctsArgs a, LeafArgs la);
 #endif
 
 // ------------------------------------------------------------------------------------
@@ -8011,6 +8326,128 @@ int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const 
         return BK_OK;
     }
     rc = finish_guarded(h, st, BK_STICKY_GUARD, BK_EOVERFLOW, "bk_mcts: step guard tripped%s");
+    return rc ? rc : take_diag(h);  // a search broke a tree invariant (mc_diag)
+}
+
+int bk_mcts_learned(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const uint8_t* players,
+                    const uint64_t* root_hash, int32_t n_games, const bk_mcts_cfg* cfg, const uint64_t* zobrist,
+                    int32_t n_zobrist, const int32_t* zobrist_index, uint64_t* tt_keys, double* tt_vals,
+                    int32_t* tt_count, const double* log_table, int32_t log_len, const bk_winprob_model* model,
+                    int32_t max_turns, double bias_weight, double* prior_bias, int32_t* bias_updates,
+                    bk_mcts_node* nodes, double* rewards, uint8_t* hit_flags, bk_mcts_out* out, int mem) {
+    if (!h || !cfg || !model || n_games < 0 || (mem != BK_MEM_HOST && mem != BK_MEM_DEVICE))
+        return set_err(h, BK_EINVAL, "bk_mcts_learned: invalid arguments%s", "");
+    if (!__builtin_isfinite(model->intercept) || !__builtin_isfinite(bias_weight))
+        return set_err(h, BK_EINVAL, "bk_mcts_learned: the model's intercept or the bias weight is not finite%s", "");
+    for (int k = 0; k < BK_SNAPSHOT_COLUMNS; ++k) {
+        if (!__builtin_isfinite(model->mean[k]) || !__builtin_isfinite(model->scale[k]) ||
+            !__builtin_isfinite(model->coef[k]))
+            return set_err(h, BK_EINVAL, "bk_mcts_learned: the model has a non-finite mean, scale or coef%s", "");
+        if (model->scale[k] == 0.0)
+            return set_err(h, BK_EINVAL, "bk_mcts_learned: the model has a scale of 0%s", "");
+    }
+    if (max_turns < 0) return set_err(h, BK_EINVAL, "bk_mcts_learned: max_turns must be >= 0%s", "");
+    if (n_games == 0) return BK_OK;
+    if (!roots || !root_sets || !players || !zobrist || n_zobrist < 1 || !zobrist_index || !log_table || log_len < 1 ||
+        !out || !bias_updates || (rewards == nullptr) != (hit_flags == nullptr) || (bias_weight != 0.0 && !prior_bias))
+        return set_err(h, BK_EINVAL, "bk_mcts_learned: missing buffer%s", "");
+    if (cfg->iterations < 0 || cfg->node_cap < 1 || cfg->time_limit_us < 0 || cfg->iter_stop < 0 ||
+        (cfg->resume != 0 && cfg->resume != 1) || cfg->flags != 0)
+        return set_err(h, BK_EINVAL, "bk_mcts_learned: bad cfg (iterations/node_cap/iter_stop/resume; flags must be 0)%s", "");
+    if (cfg->resume && !nodes)
+        return set_err(h, BK_EINVAL, "bk_mcts_learned: resume needs the caller's nodes buffer%s", "");
+    if (cfg->use_tt && (!tt_keys || !tt_vals || !tt_count || cfg->tt_cap < 2 || (cfg->tt_cap & (cfg->tt_cap - 1))))
+        return set_err(h, BK_EINVAL, "bk_mcts_learned: use_tt needs tt buffers and a power-of-two tt_cap%s", "");
+    if (mem == BK_MEM_HOST) {
+        for (int32_t g = 0; g < n_games; ++g) {
+            if (players[g] > 3 || zobrist_index[g] < 0 || zobrist_index[g] >= n_zobrist)
+                return set_err(h, BK_EINVAL, "bk_mcts_learned: bad player / zobrist_index%s", "");
+            for (int q = 0; q < 4; ++q)
+                if (root_sets[g].mask[q] + 1u > BK_FSET_SLOTS)
+                    return set_err(h, BK_EINVAL, "bk_mcts_learned: root frontier table too large%s", "");
+            if (cfg->use_tt && (tt_count[g] < 0 || tt_count[g] >= cfg->tt_cap))
+                return set_err(h, BK_EINVAL, "bk_mcts_learned: bad tt_count%s", "");
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    BK_IDLE(h, "bk_mcts_learned");
+    const size_t n = (size_t)n_games, ttc = cfg->use_tt ? (size_t)cfg->tt_cap : 0;
+    const size_t it = (size_t)cfg->iterations;
+    const int io = cfg->resume ? Staging::INOUT : Staging::OUT;  // a resumed search reads what the last one left
+    const size_t node_bytes = sizeof(bk_mcts_node) * (size_t)cfg->node_cap * n;
+    Staging st(h, mem);
+    const auto s_roots = st.in(roots, sizeof(bk_state) * n);
+    const auto s_sets = st.in(root_sets, sizeof(bk_fset) * n);
+    const auto s_players = st.in(players, n);
+    const auto s_hash = st.in(root_hash, sizeof(uint64_t) * n);
+    const auto s_zob = st.in(zobrist, sizeof(uint64_t) * MC_ZOB * (size_t)n_zobrist);
+    const auto s_zidx = st.in(zobrist_index, sizeof(int32_t) * n);
+    const auto s_ttk = st.inout(tt_keys, sizeof(uint64_t) * ttc * n);
+    const auto s_ttv = st.inout(tt_vals, sizeof(double) * ttc * n);
+    const auto s_ttn = st.inout(tt_count, cfg->use_tt ? sizeof(int32_t) * n : 0);
+    const auto s_log = st.in(log_table, sizeof(double) * (size_t)log_len);
+    const auto s_nodes = st.add(nodes, node_bytes, io);
+    const auto s_prior = st.add(bias_weight != 0.0 ? prior_bias : nullptr, sizeof(double) * (size_t)cfg->node_cap * n, io);
+    const auto s_bias = st.add(bias_updates, sizeof(int32_t) * n, io);
+    const auto s_rewards = st.add(rewards, sizeof(double) * it * n, io);
+    const auto s_hits = st.add(hit_flags, it * n, io);
+    const auto s_out = st.add(out, sizeof(bk_mcts_out) * n, io);
+    int rc = st.commit();
+    if (rc) return rc;
+    Buf* const wb = h->buf;
+    bk_mcts_node* d_nodes = s_nodes.dev();
+    if (!nodes) {  // no caller's pool: the handle's, in either memory mode
+        rc = grow(h, wb[bk_handle_s::NODES], node_bytes);
+        if (rc) return rc;
+        d_nodes = (bk_mcts_node*)wb[bk_handle_s::NODES].p;
+    }
+    const uint64_t* d_hash = s_hash.dev();
+    if (!root_hash) {  // ZobristHash.hash_board of every root, on the device (untimed)
+        rc = grow(h, wb[bk_handle_s::RH], sizeof(uint64_t) * n);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_root_hash, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->cur,
+                           s_roots.dev(), s_zob.dev(), s_zidx.dev(), (uint64_t*)wb[bk_handle_s::RH].p, n_games);
+        HIPCHK(h, hipGetLastError());
+        d_hash = (const uint64_t*)wb[bk_handle_s::RH].p;
+    }
+    // persistent grid of COOP_WAVES-search blocks; the search's McLane and slab live in LDS
+    // (DESIGN.md 4 has the kernel's resources)
+    int coop_bpc = 3;  // by LDS: 48 KB per block
+    if (tune_or(h, BK_TUNE_COOP_BLOCKS_PER_CU, 0) > 0) coop_bpc = (int)h->tune[BK_TUNE_COOP_BLOCKS_PER_CU];
+    int blocks = h->num_cu * coop_bpc;
+    const int need = (int)(((int64_t)n_games + COOP_WAVES - 1) / COOP_WAVES);
+    if (blocks > need) blocks = need;
+    if (blocks < 1) blocks = 1;
+    const uint32_t nslots = (uint32_t)blocks * COOP_WAVES;
+    int khz = 0;
+    HIPCHK(h, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->device));
+    if (khz <= 0) khz = 100000;
+    HIPCHK(h, hipMemsetAsync(h->d_counter, 0, 2 * sizeof(uint32_t), h->cur));  // [2] is sticky
+    const uint64_t per_wave = ((uint64_t)n_games + nslots - 1) / nslots + 1;
+    const uint64_t steps = 2 * per_wave * ((uint64_t)cfg->iterations + 1) * 3 + 64;  // one movegen per iteration
+    bk_mcts_cfg kcfg = *cfg;
+    kcfg.max_rollout_moves = 1;  // (unused: no rollout)
+    kcfg.rollout_policy = BK_MCTS_ROLLOUT_RANDOM;
+    MctsArgs a{s_roots.dev(), s_sets.dev(), s_players.dev(), d_hash, n_games, kcfg, s_zob.dev(), s_zidx.dev(),
+               nullptr, s_ttk.dev(), s_ttv.dev(), s_ttn.dev(), s_log.dev(), log_len, d_nodes, s_rewards.dev(),
+               s_hits.dev(), s_out.dev(), nullptr, nullptr,
+               h->d_counter, steps, (uint64_t)cfg->time_limit_us * (uint64_t)khz / 1000u, MC_TREE_BATCH, 1, 1, 1};
+    a.diag = h->d_diag;
+    a.launch_seq = ++h->mcts_launches;
+    a.state_rows = 0;
+    a.done = nullptr;
+    {
+        const size_t sb = sizeof(uint32_t) * (((size_t)n_games + 31) / 32 + 1);
+        rc = grow(h, wb[bk_handle_s::STARTED], sb);
+        if (rc) return rc;
+        a.started = (uint32_t*)wb[bk_handle_s::STARTED].p;
+        HIPCHK(h, hipMemsetAsync(a.started, 0, sb, h->cur));
+    }
+    a.coop_walk = (int)tune_or(h, BK_TUNE_COOP_WALK, a.coop_walk);
+    a.kernel_id = BK_DIAG_K_COOP_L;
+    LeafArgs la{*model, max_turns, bias_weight, s_prior.dev(), s_bias.dev()};
+    BK_LAUNCH(h, k_mcts_coop_l, dim3(blocks), dim3(COOP_WAVES * WAVE), a, la);
+    rc = finish_guarded(h, st, BK_STICKY_GUARD, BK_EOVERFLOW, "bk_mcts_learned: step guard tripped%s");
     return rc ? rc : take_diag(h);  // a search broke a tree invariant (mc_diag)
 }
 

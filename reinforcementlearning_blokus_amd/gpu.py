@@ -722,6 +722,63 @@ class BlokusGPU:
             raise RuntimeError(f"bk_mcts: {bad} searches stopped early, status bits "
                                f"{sorted(set(st[st != 0].tolist()))[:8]}")
 
+    def mcts_learned_device(self, roots, root_sets, players, root_hash, zobrist, zobrist_index, log_table, nodes, out,
+                            model, bias_updates, *, iterations: int, max_turns: int, bias_weight: float = 0.0,
+                            prior_bias=None, tt_keys=None, tt_vals=None, tt_count=None, rewards=None, hit_flags=None,
+                            exploration: float = 1.414, chunk: int = 0, time_limit_us: int = 0, check: bool = True):
+        """bk_mcts_learned with every buffer a torch CUDA tensor on this device (BK_MEM_DEVICE,
+        torch's current stream): mcts_device's searches with learned leaf evaluation in place
+        of the rollouts (k_mcts_coop_l), so there is no mt_state.  model: a WinProbModel (or a
+        BkWinprobModel).  bias_weight != 0 turns progressive bias on and needs prior_bias
+        float64[n, node_cap]; bias_updates int32[n] receives each search's update count.
+        chunk > 0 splits the searches into launches of `chunk` iterations (same result).
+        check=False leaves the status words in `out` to the caller instead of raising."""
+        import torch
+        n = roots.shape[0]
+        use_tt = tt_keys is not None
+        node_cap = nodes.shape[1] // N.MCTS_NODE_DTYPE.itemsize
+        native = model.as_native() if hasattr(model, "as_native") else model
+        tensors = dict(roots=(roots, torch.uint8, (n, 256)), root_sets=(root_sets, torch.uint8, (n, N.FSET_DTYPE.itemsize)),
+                       players=(players, torch.uint8, (n,)), zobrist_index=(zobrist_index, torch.int32, (n,)),
+                       nodes=(nodes, torch.uint8, (n, node_cap * N.MCTS_NODE_DTYPE.itemsize)),
+                       out=(out, torch.uint8, (n, N.MCTS_OUT_DTYPE.itemsize)),
+                       bias_updates=(bias_updates, torch.int32, (n,)))
+        if root_hash is not None:
+            tensors.update(root_hash=(root_hash, torch.int64, (n,)))
+        if bias_weight != 0.0:
+            if prior_bias is None:
+                raise ValueError("mcts_learned_device: a bias weight needs the prior_bias tensor")
+            tensors.update(prior_bias=(prior_bias, torch.float64, (n, node_cap)))
+        if use_tt:
+            cap = tt_keys.shape[1]
+            tensors.update(tt_keys=(tt_keys, torch.int64, (n, cap)), tt_vals=(tt_vals, torch.float64, (n, cap)),
+                           tt_count=(tt_count, torch.int32, (n,)))
+        if rewards is not None:
+            tensors.update(rewards=(rewards, torch.float64, (n, iterations)),
+                           hit_flags=(hit_flags, torch.uint8, (n, iterations)))
+        for name, (t, dt, shape) in tensors.items():
+            _check_device_tensor(t, name, dt, shape, self.device)
+        _check_device_tensor(zobrist, "zobrist", torch.int64, (zobrist.shape[0], N.MCTS_ZOBRIST_WORDS), self.device)
+        _check_device_tensor(log_table, "log_table", torch.float64, (log_table.shape[0],), self.device)
+        self._stream_from_torch()
+        d = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
+        assert not (chunk and time_limit_us), "timed searches run in one launch"
+        for j, stop in enumerate(mcts_chunks(iterations, chunk)):
+            cfg = N.BkMctsCfg(iterations, 1, float(exploration), int(use_tt), node_cap,
+                              tt_keys.shape[1] if use_tt else 0, int(time_limit_us), stop, int(j > 0), 0, 0)
+            self.handle.mcts_learned(d(roots), d(root_sets), d(players), d(root_hash), n, cfg, d(zobrist),
+                                     zobrist.shape[0], d(zobrist_index), d(tt_keys), d(tt_vals), d(tt_count),
+                                     d(log_table), log_table.shape[0], native, max_turns, bias_weight,
+                                     d(prior_bias) if bias_weight != 0.0 else 0, d(bias_updates), d(nodes),
+                                     d(rewards), d(hit_flags), d(out), N.MEM_DEVICE)
+        if not check:
+            return
+        st = out.view(torch.int32)[:, 6]
+        bad = int((st != 0).sum().item())
+        if bad:
+            raise RuntimeError(f"bk_mcts_learned: {bad} searches stopped early, status bits "
+                               f"{sorted(set(st[st != 0].tolist()))[:8]}")
+
 
 class SnapSlots:
     """The checkpoint slots of n games for arena_step(snap=...): ``plies`` the plies the

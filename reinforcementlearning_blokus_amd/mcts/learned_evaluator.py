@@ -142,6 +142,13 @@ class WinProbModel:
             self.__dict__["_native"] = native
         return native
 
+    def key(self):
+        """The model's values as one hashable (cached): equal keys, the same arithmetic."""
+        k = self.__dict__.get("_key")
+        if k is None:
+            k = self.__dict__["_key"] = (tuple(self.mean), tuple(self.scale), tuple(self.coef), self.intercept)
+        return k
+
     def pair_logit(self, row_p: Sequence[float], row_q: Sequence[float]) -> float:
         """t of player p against q: the kernel's chain, one rounding per operation."""
         t = 0.0

@@ -6,7 +6,7 @@ transposition cache follow mcts/mcts_agent.py:19-191, :304-437, :572-582.
 
 Rollouts (mcts/mcts_agent.py:470-554, <= max_rollout_moves plies, stop at the first
 player without a move, reward = final - initial Board.get_score of the root player)
-have three GPU backends:
+have three GPU backends (and leaf evaluation a fourth, below):
 
 * ``rollout_backend="search"`` (the default, for the reference's default HeuristicAgent
   rollout agent and for a RandomAgent): the WHOLE search -- selection, expansion, TT
@@ -28,7 +28,19 @@ The reference's learned-evaluator options (leaf evaluation, progressive bias, po
 shaping; mcts/mcts_agent.py:376, :398-404, :426-468, :487-552) run on the ``exact`` backend:
 the host tree asks mcts.learned_evaluator for win probabilities, one bk_winprob_eval launch
 per call (parent and child of a progressive-bias update share a launch).  The in-kernel
-searches do not evaluate leaves, so ``search`` and ``kernel`` reject these options.
+searches of ``search`` and ``kernel`` do not evaluate leaves and reject these options.
+
+* ``rollout_backend="leaf"`` (opt-in; ``leaf_evaluation_enabled`` with a ``pairwise_logreg``
+  model, optionally ``progressive_bias_enabled``): the whole search -- selection, expansion,
+  TT, the learned leaf evaluation, progressive bias, backpropagation -- runs in one
+  bk_mcts_learned launch (k_mcts_coop_l).  Every value is bit for bit what bk_winprob_eval
+  returns for the same board, so the search equals the ``exact`` backend's.  There is no
+  rollout: ``rollout_agent`` is not used and its stream is never touched.  ``search_batch``
+  takes leaf agents too (one launch per parameter group).  Potential shaping needs rollouts
+  and stays on ``exact``; so do progressive bias without leaf evaluation, a
+  ``dummy_model.json`` evaluator, and progressive bias with a weight of 0 (the kernel reads
+  weight 0 as bias off, the host tree would still count its updates): each raises a
+  ``ValueError`` that names ``exact``.
 """
 from __future__ import annotations
 
@@ -46,6 +58,93 @@ from ..engine.pieces import PieceGenerator
 from .zobrist import TranspositionTable, ZobristHash
 
 
+def _tt_gather(gpu, ags, iters, dev):
+    """The agents' device TT rows (leased or grown as needed) gathered into one launch's
+    [n, cap] block: (pool, rows, keys, vals, count).  Called under TT_LOCK."""
+    import torch
+
+    from ..gpu import TTPool
+    cap = max([a._gpu_tt.cap for a in ags if a._gpu_tt is not None] or [1 << 12])
+    need = max([int(a._gpu_tt.count[0]) for a in ags if a._gpu_tt is not None] or [0]) + iters + 2
+    while 2 * need > cap:
+        cap *= 2
+    pool = TTPool.get(gpu.device, cap)
+    for a in ags:
+        row = a._gpu_tt
+        if row is None:
+            a._gpu_tt = pool.lease()
+        elif row.pool is not pool:  # grown: re-insert into a row of the larger pool
+            nr = pool.lease()
+            nr.load(*row.items(0))
+            row.release()
+            a._gpu_tt = nr
+    rows = torch.tensor([a._gpu_tt.row for a in ags], dtype=torch.int64, device=dev)
+    return (pool, rows, pool.keys.index_select(0, rows), pool.vals.index_select(0, rows),
+            pool.count.index_select(0, rows))
+
+
+def _tt_scatter(ags, pool, rows, tk, tv, tc):
+    """The launch's TT block back into the agents' rows (synchronizes the stream)."""
+    pool.keys.index_copy_(0, rows, tk)
+    pool.vals.index_copy_(0, rows, tv)
+    pool.count.index_copy_(0, rows, tc)
+    for a, cnt in zip(ags, tc.cpu().numpy()):
+        a._gpu_tt.count[0] = cnt
+
+
+def _leaf_search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, iters, c, use_tt, tl_us, model, max_turns, bias_w):
+    """One bk_mcts_learned launch for search_packed's leaf agents, every buffer in HBM; the
+    TT rows as in _search_on_device.  Returns dict(out, rewards, hit_flags, bias_updates,
+    children): children[j] = the root's children of search j as [move, visits, total,
+    prior_bias] in expansion order."""
+    import torch
+
+    from .. import _native as N
+    from ..gpu import TT_LOCK, mcts_log_table, mcts_node_cap
+    n = len(ags)
+    dev = f"cuda:{gpu.device}"
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    lts = gpu.__dict__.setdefault("_log_tables", {})
+    if iters not in lts:
+        lts[iters] = up(mcts_log_table(iters))
+    cap_nodes = mcts_node_cap(iters)
+    d_out = torch.zeros((n, N.MCTS_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_rew = torch.empty((n, iters), dtype=torch.float64, device=dev)
+    d_flags = torch.empty((n, iters), dtype=torch.uint8, device=dev)
+    d_nodes = torch.empty((n, cap_nodes * N.MCTS_NODE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    d_prior = torch.zeros((n, cap_nodes), dtype=torch.float64, device=dev) if bias_w != 0.0 else None
+    d_bias = torch.zeros(n, dtype=torch.int32, device=dev)
+    tk = tv = tc = None
+    with (TT_LOCK if use_tt else contextlib.nullcontext()):
+        if use_tt:
+            pool, rows, tk, tv, tc = _tt_gather(gpu, ags, iters, dev)
+        gpu.mcts_learned_device(up(rts.view(np.uint8).reshape(n, 256)), up(sts.view(np.uint8).reshape(n, -1)), up(pl),
+                                up(rh.view(np.int64)), up(zob.view(np.int64)), up(zidx), lts[iters], d_nodes, d_out,
+                                model, d_bias, iterations=iters, max_turns=max_turns, bias_weight=bias_w,
+                                prior_bias=d_prior, tt_keys=tk, tt_vals=tv, tt_count=tc, rewards=d_rew,
+                                hit_flags=d_flags, exploration=c, time_limit_us=tl_us)
+        if use_tt:
+            _tt_scatter(ags, pool, rows, tk, tv, tc)
+    out = d_out.cpu().numpy().view(N.MCTS_OUT_DTYPE).reshape(n)
+    live = max(1, int(out["iterations_run"].max())) if n else 1
+    # the roots' child blocks (and their prior biases) in one gather each
+    root = d_nodes.view(n, cap_nodes, N.MCTS_NODE_DTYPE.itemsize)[:, 0, :].cpu().numpy().view(N.MCTS_NODE_DTYPE).reshape(n)
+    where = np.concatenate([j * cap_nodes + int(root["child0"][j]) + np.arange(int(root["n_exp"][j]), dtype=np.int64)
+                            for j in range(n)] or [np.zeros(0, np.int64)])
+    d_where = torch.from_numpy(where).to(dev)
+    kids = d_nodes.view(n * cap_nodes, N.MCTS_NODE_DTYPE.itemsize).index_select(0, d_where).cpu().numpy()
+    kids = kids.view(N.MCTS_NODE_DTYPE).reshape(-1)
+    pri = d_prior.view(-1).index_select(0, d_where).cpu().numpy() if d_prior is not None else np.zeros(len(where))
+    children, at = [], 0
+    for j in range(n):
+        k = int(root["n_exp"][j])
+        children.append([[int(kids["move"][at + i]), int(kids["visits"][at + i]), float(kids["total"][at + i]),
+                          float(pri[at + i])] for i in range(k)])
+        at += k
+    return {"out": out, "rewards": d_rew[:, :live].cpu().numpy(), "hit_flags": d_flags[:, :live].cpu().numpy(),
+            "bias_updates": d_bias.cpu().numpy(), "children": children}
+
+
 def _search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, mt, iters, max_roll, c, use_tt, tl_us, policy):
     """One bk_mcts launch for search_packed with every buffer in HBM (BK_MEM_DEVICE).
     The agents' TTs stay on the device between calls (TTPool rows, gathered into the
@@ -55,7 +154,7 @@ def _search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, mt, iters, max_roll
     import torch
 
     from .. import _native as N
-    from ..gpu import TT_LOCK, TTPool, mcts_log_table, mcts_node_cap
+    from ..gpu import TT_LOCK, mcts_log_table, mcts_node_cap
     n = len(ags)
     dev = f"cuda:{gpu.device}"
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
@@ -72,23 +171,7 @@ def _search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, mt, iters, max_roll
     # copy): another thread's search or pool growth cannot interleave (gpu.TT_LOCK)
     with (TT_LOCK if use_tt else contextlib.nullcontext()):
         if use_tt:
-            cap = max([a._gpu_tt.cap for a in ags if a._gpu_tt is not None] or [1 << 12])
-            need = max([int(a._gpu_tt.count[0]) for a in ags if a._gpu_tt is not None] or [0]) + iters + 2
-            while 2 * need > cap:
-                cap *= 2
-            pool = TTPool.get(gpu.device, cap)
-            for a in ags:
-                row = a._gpu_tt
-                if row is None:
-                    a._gpu_tt = pool.lease()
-                elif row.pool is not pool:  # grown: re-insert into a row of the larger pool
-                    nr = pool.lease()
-                    nr.load(*row.items(0))
-                    row.release()
-                    a._gpu_tt = nr
-            rows = torch.tensor([a._gpu_tt.row for a in ags], dtype=torch.int64, device=dev)
-            tk, tv, tc = (pool.keys.index_select(0, rows), pool.vals.index_select(0, rows),
-                          pool.count.index_select(0, rows))
+            pool, rows, tk, tv, tc = _tt_gather(gpu, ags, iters, dev)
         gpu.mcts_device(up(rts.view(np.uint8).reshape(n, 256)), up(sts.view(np.uint8).reshape(n, -1)), up(pl),
                         up(rh.view(np.int64)), up(zob.view(np.int64)), up(zidx), d_mt, lts[iters],
                         torch.empty((n, cap_nodes * N.MCTS_NODE_DTYPE.itemsize), dtype=torch.uint8, device=dev),
@@ -96,11 +179,7 @@ def _search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, mt, iters, max_roll
                         hit_flags=d_flags, max_rollout_moves=max_roll, exploration=c, rollout_policy=policy,
                         time_limit_us=tl_us)
         if use_tt:
-            pool.keys.index_copy_(0, rows, tk)
-            pool.vals.index_copy_(0, rows, tv)
-            pool.count.index_copy_(0, rows, tc)
-            for a, cnt in zip(ags, tc.cpu().numpy()):  # synchronizes this stream
-                a._gpu_tt.count[0] = cnt
+            _tt_scatter(ags, pool, rows, tk, tv, tc)  # synchronizes this stream
     mt[:] = d_mt.cpu().numpy().view(np.uint32)
     out = d_out.cpu().numpy().view(N.MCTS_OUT_DTYPE).reshape(n)
     # only the iterations some search ran cross PCIe (a timed search's bound is far above)
@@ -249,6 +328,18 @@ class MCTSAgent:
             raise ValueError("learned_model_path is required when learned evaluation, progressive bias, "
                              "or potential shaping is enabled.")
         learned = bool(self._requires_learned_evaluator or self.learned_model_path)
+        if rollout_backend == "leaf":
+            if self.potential_shaping_enabled:
+                raise ValueError("rollout_backend='leaf': potential shaping needs rollouts; use rollout_backend='exact'")
+            if self.progressive_bias_enabled and not self.leaf_evaluation_enabled:
+                raise ValueError("rollout_backend='leaf' runs progressive bias only together with leaf evaluation; "
+                                 "use rollout_backend='exact'")
+            if not self.leaf_evaluation_enabled:
+                raise ValueError("rollout_backend='leaf' needs leaf_evaluation_enabled=True and a learned_model_path; "
+                                 "without leaf evaluation use rollout_backend='search' or 'exact'")
+            if self.progressive_bias_enabled and float(progressive_bias_weight) == 0.0:
+                raise ValueError("rollout_backend='leaf': a progressive_bias_weight of 0 turns the bias off in the "
+                                 "kernel; use rollout_backend='exact'")
         if learned and rollout_backend in ("search", "kernel"):
             raise ValueError(f"rollout_backend='{rollout_backend}': the in-kernel search does not evaluate leaves; "
                              "the learned-evaluator options need rollout_backend='exact'")
@@ -271,8 +362,8 @@ class MCTSAgent:
         if rollout_backend is None:
             rollout_backend = "search" if _search_policy(rollout_agent) is not None else "exact"
         self.rollout_backend = rollout_backend
-        if self.rollout_backend not in ("search", "exact", "kernel"):
-            raise ValueError("rollout_backend must be 'search', 'exact' or 'kernel'")
+        if self.rollout_backend not in ("search", "exact", "kernel", "leaf"):
+            raise ValueError("rollout_backend must be 'search', 'exact', 'kernel' or 'leaf'")
         if self.rollout_backend == "exact" and rollout_agent is None:
             raise ValueError("rollout_backend='exact' needs a rollout_agent")
         if self.rollout_backend == "search" and _search_policy(rollout_agent) is None:
@@ -287,8 +378,18 @@ class MCTSAgent:
         self.learned_evaluator = None
         if self.learned_model_path:
             from .learned_evaluator import LearnedWinProbabilityEvaluator
-            self.learned_evaluator = LearnedWinProbabilityEvaluator(self.learned_model_path,
-                                                                    potential_mode=potential_mode, device=device)
+            try:
+                self.learned_evaluator = LearnedWinProbabilityEvaluator(self.learned_model_path,
+                                                                        potential_mode=potential_mode, device=device)
+            except ValueError as e:
+                if self.rollout_backend != "leaf":
+                    raise
+                raise ValueError(f"rollout_backend='leaf' needs a pairwise_logreg model ({e}); other evaluators "
+                                 "belong to rollout_backend='exact'") from None
+            if self.rollout_backend == "leaf" and self.learned_evaluator.model_type != "pairwise_logreg":
+                raise ValueError(f"rollout_backend='leaf' needs a pairwise_logreg model, {self.learned_model_path} is "
+                                 f"a {self.learned_evaluator.model_type} evaluator; use rollout_backend='exact'")
+        self.last_root_children: List[List[float]] = []  # "leaf": [move, visits, total, prior_bias] per root child
         self.stats = self._fresh_stats()
 
     @staticmethod
@@ -303,7 +404,7 @@ class MCTSAgent:
             return None
         if len(legal_moves) == 1:
             return legal_moves[0]
-        if self.rollout_backend == "search":
+        if self.rollout_backend in ("search", "leaf"):
             return MCTSAgent.search_batch([self], [board], [player], [legal_moves])[0]
         t0 = time.time()
         root = MCTSNode(board, player)
@@ -327,12 +428,14 @@ class MCTSAgent:
     def search_batch(agents: List["MCTSAgent"], boards: List[Board], players: List[Player],
                      legal_moves: Optional[List[List[Move]]] = None) -> List[Optional[Move]]:
         """select_action for several "search"-backend agents in ONE bk_mcts launch (one
-        search per agent; an agent appears at most once).  Each result equals the
-        agent's own select_action on that position: the search reads and advances the
-        agent's rollout stream and TT, and updates its stats, exactly as the
-        reference's select_action (mcts/mcts_agent.py:304-341) does.  Positions with
-        < 2 legal moves are answered without a search (:313-318); ``legal_moves[i]`` is
-        the caller's legal list for position i (generated here when omitted)."""
+        search per agent; an agent appears at most once).  "leaf" agents may be among them:
+        they go to bk_mcts_learned launches of their own (never in a group with "search"
+        agents).  Each result equals the agent's own select_action on that position: the
+        search reads and advances the agent's rollout stream and TT, and updates its stats,
+        exactly as the reference's select_action (mcts/mcts_agent.py:304-341) does.
+        Positions with < 2 legal moves are answered without a search (:313-318);
+        ``legal_moves[i]`` is the caller's legal list for position i (generated here when
+        omitted)."""
         assert len(agents) == len(boards) == len(players)
         gen = get_shared_generator()
         legal = [legal_moves[i] if legal_moves is not None else gen.get_legal_moves(b, p)
@@ -360,8 +463,8 @@ class MCTSAgent:
         out: List[Optional[int]] = [None] * len(agents)
         groups = {}  # agents sharing (iterations, rollout cap, c, TT on/off, time limit) share a launch
         for i, a in enumerate(agents):
-            if a.rollout_backend != "search":
-                raise ValueError("search_batch needs rollout_backend='search' agents")
+            if a.rollout_backend not in ("search", "leaf"):
+                raise ValueError("search_batch needs rollout_backend='search' or 'leaf' agents")
             # time_limit (seconds, mcts_agent.py:325-333, :349-356): iterate until it runs
             # out, ignoring `iterations`, as _run_mcts_with_time_limit does.  The kernel stops
             # each search at the first iteration boundary past the limit; the launch still
@@ -373,13 +476,24 @@ class MCTSAgent:
             iters = int(a.iterations)
             if tl_us:
                 iters = int(min(TIMED_MAX_ITERS, max(16, math.ceil(float(a.time_limit) * TIMED_MAX_ITERS_PER_S))))
+            if a.rollout_backend == "leaf":  # one launch per (iterations, c, TT, time limit, model values, max_turns, bias)
+                ev = a.learned_evaluator
+                bias_w = a.progressive_bias_weight if a.progressive_bias_enabled else 0.0
+                key = ("leaf", iters, float(a.exploration_constant), a.use_transposition_table, tl_us, ev.model.key(),
+                       int(ev.max_turns), float(bias_w))
+                groups.setdefault(key, []).append(i)
+                continue
             policy = _search_policy(a.rollout_agent)
             if policy is None:
                 raise ValueError("search_batch: the rollout agent cannot be replayed on the GPU")
             key = (iters, a.max_rollout_moves, float(a.exploration_constant), a.use_transposition_table,
                    tl_us, policy)
             groups.setdefault(key, []).append(i)
-        for (iters, max_roll, c, use_tt, tl_us, policy), idx in groups.items():
+        for key, idx in groups.items():
+            if key[0] == "leaf":
+                MCTSAgent._leaf_group(agents, roots, sets, players, key, idx, out)
+                continue
+            iters, max_roll, c, use_tt, tl_us, policy = key
             ags = [agents[i] for i in idx]
             gpu = BlokusGPU.shared(ags[0].device)
             rts = np.ascontiguousarray(roots[idx])
@@ -455,6 +569,62 @@ class MCTSAgent:
                         a._gpu_tt = None
                 out[i] = f_best[j] if f_best[j] >= 0 else None
         return out
+
+    @staticmethod
+    def _leaf_group(agents, roots, sets, players, key, idx, out) -> None:
+        """search_packed's launch for one group of "leaf" agents; stats as the exact backend
+        leaves them (leaf_eval_calls, progressive_bias_updates, the non-hit rewards)."""
+        from ..gpu import BlokusGPU
+        from .zobrist import flat_keys, hash_states
+        _, iters, c, use_tt, tl_us, _, max_turns, bias_w = key
+        ags = [agents[i] for i in idx]
+        gpu = BlokusGPU.shared(ags[0].device)
+        rts = np.ascontiguousarray(roots[idx])
+        sts = np.ascontiguousarray(sets[idx])
+        pl = np.array([players[i] for i in idx], np.uint8)
+        rts["current_player"] = pl
+        zob = np.stack([flat_keys(a.zobrist_hash) for a in ags])
+        rh = hash_states(rts, zob)  # one table per search
+        t0 = time.time()
+        r = _leaf_search_on_device(gpu, ags, rts, sts, pl, rh, zob, np.arange(len(ags), dtype=np.int32), iters, c,
+                                   use_tt, tl_us, ags[0].learned_evaluator.model, max_turns, bias_w)
+        dt = time.time() - t0
+        kms, ro = gpu.last_kernel_ms(), r["out"]
+        for tot in (SEARCH_TOTALS, SEARCH_TOTALS["by_kernel"].setdefault(
+                gpu.last_kernel(), {"launches": 0, "kernel_ms": 0.0, "sims": 0, "rollout_plies": 0})):
+            tot["launches"] += 1
+            tot["kernel_ms"] += kms
+            tot["sims"] += int(ro["iterations_run"].sum())
+        its = np.arange(r["rewards"].shape[1])[None, :]
+        live = (r["hit_flags"] == 0) & (its < ro["iterations_run"][:, None])
+        rew_rows = np.where(live, r["rewards"], np.nan).tolist()
+        for j, (i, a) in enumerate(zip(idx, ags)):
+            n_it, hits, evals = int(ro["iterations_run"][j]), int(ro["tt_hits"][j]), int(ro["rollouts"][j])
+            a.stats["iterations_run"] = n_it
+            a.stats["last_search_uncertified"] = False
+            if tl_us:
+                a.stats["iteration_bound"] = iters
+                a.stats["iteration_bound_reached"] = n_it >= iters
+                if a.stats["iteration_bound_reached"]:
+                    warnings.warn(f"MCTSAgent: a {a.time_limit} s search stopped at its {iters}-iteration "
+                                  "bound before the time ran out", RuntimeWarning, stacklevel=2)
+            a.stats["time_elapsed"] = dt
+            a.stats["transposition_hits"] += hits
+            a.stats["leaf_eval_calls"] += evals
+            a.stats["progressive_bias_updates"] += int(r["bias_updates"][j])
+            a.stats["rollout_rewards"].extend([x for x in rew_rows[j] if x == x])
+            a.last_root_children = r["children"][j]
+            if use_tt:
+                t = a.transposition_table
+                t.access_count += hits + evals
+                t.hit_count += hits
+                t.gpu_size = int(a._gpu_tt.count[0])
+                if t.gpu_size > 500000:  # mcts_agent.py:338-339
+                    t.clear()
+                    a._gpu_tt.release()
+                    a._gpu_tt = None
+            best = int(ro["best_move"][j])
+            out[i] = best if best >= 0 else None
 
     def _get_move_positions(self, move: Move) -> List[Position]:
         return _positions(move)
