@@ -845,7 +845,7 @@ def _run_games_device(run_config: RunConfig, idx: List[int], seats: List[Mapping
     from .. import _native as N
     from ..agents.fast_mcts_agent import _log_table
     from ..gpu import BlokusGPU, SnapSlots, empty_state, mcts_log_table, mcts_node_cap
-    from ..mcts.mcts_agent import SEARCH_TOTALS
+    from ..mcts.mcts_agent import add_search_launch
     mcts, fast, seat_kind, seat_agent = agents_dev
     n = len(idx)
     cfgs = {a.name: a for a in run_config.agents}
@@ -1102,12 +1102,7 @@ def _run_games_device(run_config: RunConfig, idx: List[int], seats: List[Mapping
         if len(games):  # a launch lasts as long as its longest search: its work against the mean
             pl = o["rollout_plies"].astype(np.float64)
             tl["job_plies_max_over_mean"] += float(pl.max() / max(pl.mean(), 1.0))
-        for t in (SEARCH_TOTALS, SEARCH_TOTALS["by_kernel"].setdefault(
-                eng.last_kernel(), {"launches": 0, "kernel_ms": 0.0, "sims": 0, "rollout_plies": 0})):
-            t["launches"] += 1
-            t["kernel_ms"] += kms
-            t["sims"] += int(its.sum())
-            t["rollout_plies"] += kplies
+        add_search_launch(eng.last_kernel(), kms, int(its.sum()), kplies)
         if job.get("early"):
             rest = np.flatnonzero(job["left"])
             if len(rest):  # (the launch has ended: its out records are complete)

@@ -7082,8 +7082,8 @@ static int clear_own_sticky(bk_handle h, uint32_t sticky, uint32_t own) {
 #define BK_IDLE(h, name)                                                                \
     do {                                                                                \
         if ((h)->busy)                                                                  \
-            return set_err((h), BK_EINVAL, name ": an asynchronous bk_mcts search is still running on " \
-                                           "this handle (bk_synchronize first)%s", "");  \
+            return set_err((h), BK_EINVAL, "%s: an asynchronous bk_mcts search is still running on "  \
+                                           "this handle (bk_synchronize first)", name);  \
     } while (0)
 
 // A pending bk_mcts failure record (mc_diag) moves to the host copy and is reported once
@@ -7205,6 +7205,128 @@ static int finish_guarded(bk_handle h, Staging& st, uint32_t own, int code, cons
     if (int rc = clear_own_sticky(h, ctr[2], own)) return rc;  // reported here
     return ctr[1] ? set_err(h, code, msg, "") : BK_OK;
 }
+
+// What bk_mcts and bk_mcts_learned do alike, in the order their bodies call it: the checks
+// of the arguments both take (check_buffers, check_games), those buffers' staging sections
+// (stage; the entry point adds its own to `st` before commit), the node pool, root hashes,
+// time limit and counter (commit), the launch's bookkeeping in MctsArgs (arm) and the wait
+// for a synchronous launch (finish).  What only one of them takes or decides -- its other
+// arguments and sections, the kernel, the grid, the step bound -- stays in its body.
+struct MctsCall {
+    bk_handle h;
+    const char* name;  // the entry point, for the messages
+    const bk_state* roots; const bk_fset* root_sets; const uint8_t* players; const uint64_t* root_hash;
+    int32_t n_games; const bk_mcts_cfg* cfg; const uint64_t* zobrist; int32_t n_zobrist; const int32_t* zobrist_index;
+    uint64_t* tt_keys; double* tt_vals; int32_t* tt_count; const double* log_table; int32_t log_len;
+    bk_mcts_node* nodes; double* rewards; uint8_t* hit_flags; bk_mcts_out* out; int mem;
+    Staging st{h, mem};
+    int io = 0;  // the direction of what a resumed search reads back (set by stage)
+    Staging::Ref<const bk_state> s_roots{}; Staging::Ref<const bk_fset> s_sets{}; Staging::Ref<const uint8_t> s_players{};
+    Staging::Ref<const uint64_t> s_hash{}, s_zob{}; Staging::Ref<const int32_t> s_zidx{}; Staging::Ref<uint64_t> s_ttk{};
+    Staging::Ref<double> s_ttv{}; Staging::Ref<int32_t> s_ttn{}; Staging::Ref<const double> s_log{};
+    Staging::Ref<bk_mcts_node> s_nodes{}; Staging::Ref<double> s_rewards{}; Staging::Ref<uint8_t> s_hits{};
+    Staging::Ref<bk_mcts_out> s_out{};
+    bk_mcts_node* d_nodes = nullptr;  // the caller's pool or the handle's
+    const uint64_t* d_hash = nullptr;  // the caller's root hashes or k_root_hash's
+    uint64_t time_ticks = 0;  // cfg->time_limit_us in wall-clock ticks
+
+    bool bad_args() const { return !h || !cfg || n_games < 0 || (mem != BK_MEM_HOST && mem != BK_MEM_DEVICE); }
+
+    // own_missing / own_bad_cfg: the entry point's verdict on the buffers and cfg fields only
+    // it takes, reported with the shared ones (cfg_msg names the fields it checks)
+    int check_buffers(bool own_missing, bool own_bad_cfg, const char* cfg_msg) {
+        if (!roots || !root_sets || !players || !zobrist || n_zobrist < 1 || !zobrist_index || !log_table ||
+            log_len < 1 || !out || (rewards == nullptr) != (hit_flags == nullptr) || own_missing)
+            return set_err(h, BK_EINVAL, "%s: missing buffer", name);
+        if (cfg->iterations < 0 || cfg->node_cap < 1 || cfg->time_limit_us < 0 || cfg->iter_stop < 0 ||
+            (cfg->resume != 0 && cfg->resume != 1) || own_bad_cfg)
+            return set_err(h, BK_EINVAL, cfg_msg, "");
+        if (cfg->resume && !nodes) return set_err(h, BK_EINVAL, "%s: resume needs the caller's nodes buffer", name);
+        return BK_OK;
+    }
+
+    // own_bad_game(g): the entry point's per-game check, reported with player / zobrist_index
+    template <class F> int check_games(F own_bad_game, const char* game_msg) {
+        if (cfg->use_tt && (!tt_keys || !tt_vals || !tt_count || cfg->tt_cap < 2 || (cfg->tt_cap & (cfg->tt_cap - 1))))
+            return set_err(h, BK_EINVAL, "%s: use_tt needs tt buffers and a power-of-two tt_cap", name);
+        if (mem != BK_MEM_HOST) return BK_OK;
+        for (int32_t g = 0; g < n_games; ++g) {
+            if (players[g] > 3 || zobrist_index[g] < 0 || zobrist_index[g] >= n_zobrist || own_bad_game(g))
+                return set_err(h, BK_EINVAL, game_msg, "");
+            for (int q = 0; q < 4; ++q)
+                if (root_sets[g].mask[q] + 1u > BK_FSET_SLOTS)
+                    return set_err(h, BK_EINVAL, "%s: root frontier table too large", name);
+            if (cfg->use_tt && (tt_count[g] < 0 || tt_count[g] >= cfg->tt_cap))
+                return set_err(h, BK_EINVAL, "%s: bad tt_count", name);
+        }
+        return BK_OK;
+    }
+
+    int stage() {
+        HIPCHK(h, hipSetDevice(h->device));
+        BK_IDLE(h, name);
+        const size_t n = (size_t)n_games, ttc = cfg->use_tt ? (size_t)cfg->tt_cap : 0, it = (size_t)cfg->iterations;
+        io = cfg->resume ? Staging::INOUT : Staging::OUT;  // a resumed search reads what the last one left
+        s_roots = st.in(roots, sizeof(bk_state) * n);
+        s_sets = st.in(root_sets, sizeof(bk_fset) * n);
+        s_players = st.in(players, n);
+        s_hash = st.in(root_hash, sizeof(uint64_t) * n);
+        s_zob = st.in(zobrist, sizeof(uint64_t) * MC_ZOB * (size_t)n_zobrist);
+        s_zidx = st.in(zobrist_index, sizeof(int32_t) * n);
+        s_ttk = st.inout(tt_keys, sizeof(uint64_t) * ttc * n);
+        s_ttv = st.inout(tt_vals, sizeof(double) * ttc * n);
+        s_ttn = st.inout(tt_count, cfg->use_tt ? sizeof(int32_t) * n : 0);
+        s_log = st.in(log_table, sizeof(double) * (size_t)log_len);
+        s_nodes = st.add(nodes, sizeof(bk_mcts_node) * (size_t)cfg->node_cap * n, io);
+        s_rewards = st.add(rewards, sizeof(double) * it * n, io);
+        s_hits = st.add(hit_flags, it * n, io);
+        s_out = st.add(out, sizeof(bk_mcts_out) * n, io);
+        return BK_OK;
+    }
+
+    int commit() {
+        if (int rc = st.commit()) return rc;
+        const size_t n = (size_t)n_games;
+        Buf* const wb = h->buf;  // the work buffers, by bk_handle_s's names
+        d_nodes = s_nodes.dev();
+        if (!nodes) {  // no caller's pool: the handle's, in either memory mode
+            if (int rc = grow(h, wb[bk_handle_s::NODES], sizeof(bk_mcts_node) * (size_t)cfg->node_cap * n)) return rc;
+            d_nodes = (bk_mcts_node*)wb[bk_handle_s::NODES].p;
+        }
+        d_hash = s_hash.dev();
+        if (!root_hash) {  // ZobristHash.hash_board of every root, on the device (untimed)
+            if (int rc = grow(h, wb[bk_handle_s::RH], sizeof(uint64_t) * n)) return rc;
+            hipLaunchKernelGGL(k_root_hash, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->cur,
+                               s_roots.dev(), s_zob.dev(), s_zidx.dev(), (uint64_t*)wb[bk_handle_s::RH].p, n_games);
+            HIPCHK(h, hipGetLastError());
+            d_hash = (const uint64_t*)wb[bk_handle_s::RH].p;
+        }
+        int khz = 0;
+        HIPCHK(h, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->device));
+        if (khz <= 0) khz = 100000;
+        time_ticks = (uint64_t)cfg->time_limit_us * (uint64_t)khz / 1000u;
+        HIPCHK(h, hipMemsetAsync(h->d_counter, 0, 2 * sizeof(uint32_t), h->cur));  // [2] is sticky
+        return BK_OK;
+    }
+
+    // the members of `a` every search launch sets the same way
+    int arm(MctsArgs& a) {
+        a.diag = h->d_diag;
+        a.launch_seq = ++h->mcts_launches;
+        const size_t sb = sizeof(uint32_t) * (((size_t)n_games + 31) / 32 + 1);
+        Buf& started = h->buf[bk_handle_s::STARTED];
+        if (int rc = grow(h, started, sb)) return rc;
+        a.started = (uint32_t*)started.p;
+        HIPCHK(h, hipMemsetAsync(a.started, 0, sb, h->cur));
+        a.coop_walk = (int)tune_or(h, BK_TUNE_COOP_WALK, a.coop_walk);
+        return BK_OK;
+    }
+
+    int finish(const char* guard_msg) {
+        const int rc = finish_guarded(h, st, BK_STICKY_GUARD, BK_EOVERFLOW, guard_msg);
+        return rc ? rc : take_diag(h);  // a search broke a tree invariant (mc_diag)
+    }
+};
 
 extern "C" {
 
@@ -7836,6 +7958,20 @@ int bk_step_metrics(bk_handle h, const bk_state* before, const bk_fset* sets_bef
 
 int bk_winprob_model_size(void) { return (int)sizeof(bk_winprob_model); }
 
+// a model an entry point (`name`) can hand to the kernels: every number finite, no scale of 0
+static int check_winprob_model(bk_handle h, const char* name, const bk_winprob_model* model) {
+    if (!__builtin_isfinite(model->intercept))
+        return set_err(h, BK_EINVAL, "%s: the model's intercept is not finite", name);
+    for (int k = 0; k < BK_SNAPSHOT_COLUMNS; ++k) {
+        if (!__builtin_isfinite(model->mean[k]) || !__builtin_isfinite(model->scale[k]) ||
+            !__builtin_isfinite(model->coef[k]))
+            return set_err(h, BK_EINVAL, "%s: the model has a non-finite mean, scale or coef", name);
+        if (model->scale[k] == 0.0)
+            return set_err(h, BK_EINVAL, "%s: the model has a scale of 0", name);
+    }
+    return BK_OK;
+}
+
 int bk_winprob_eval(bk_handle h, const bk_state* states, const bk_fset* sets, int32_t n, const int32_t* turn_index,
                     int32_t max_turns, const bk_winprob_model* model, double* prob, double* pair_logit, uint8_t* status,
                     int mem) {
@@ -7846,15 +7982,7 @@ int bk_winprob_eval(bk_handle h, const bk_state* states, const bk_fset* sets, in
                                  ((uintptr_t)pair_logit & 7) || ((uintptr_t)turn_index & 3)))
         return set_err(h, BK_EINVAL, "bk_winprob_eval: sets must be 16-byte, states, prob and pair_logit 8-byte, "
                                      "turn_index 4-byte aligned%s", "");
-    if (!__builtin_isfinite(model->intercept))
-        return set_err(h, BK_EINVAL, "bk_winprob_eval: the model's intercept is not finite%s", "");
-    for (int k = 0; k < BK_SNAPSHOT_COLUMNS; ++k) {
-        if (!__builtin_isfinite(model->mean[k]) || !__builtin_isfinite(model->scale[k]) ||
-            !__builtin_isfinite(model->coef[k]))
-            return set_err(h, BK_EINVAL, "bk_winprob_eval: the model has a non-finite mean, scale or coef%s", "");
-        if (model->scale[k] == 0.0)
-            return set_err(h, BK_EINVAL, "bk_winprob_eval: the model has a scale of 0%s", "");
-    }
+    if (int rc = check_winprob_model(h, "bk_winprob_eval", model)) return rc;
     if (n == 0) return BK_OK;
     HIPCHK(h, hipSetDevice(h->device));
     BK_IDLE(h, "bk_winprob_eval");
@@ -7872,15 +8000,24 @@ int bk_winprob_eval(bk_handle h, const bk_state* states, const bk_fset* sets, in
     return st.finish();
 }
 
-int bk_arena_advance(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const bk_rollout_cfg* cfg,
-                     const uint8_t* seat_masks, uint32_t* rng_state, bk_result* out, int mem) {
+// What the three arena entry points (`name`) check alike: the buffers every one of them
+// takes, the one configuration k_rollout_fr_h plays them in, and rng_state's alignment
+static int check_arena_call(bk_handle h, const char* name, const bk_state* states, const bk_fset* sets, int32_t n,
+                            const bk_rollout_cfg* cfg, const uint8_t* seat_masks, const uint32_t* rng_state,
+                            const bk_result* out, int mem) {
     if (!h || !states || !sets || !cfg || !seat_masks || !rng_state || !out || n < 0)
-        return set_err(h, BK_EINVAL, "bk_arena_advance: invalid arguments%s", "");
+        return set_err(h, BK_EINVAL, "%s: invalid arguments", name);
     if (cfg->semantics != BK_SEM_ARENA || cfg->order != BK_ORDER_FRONTIER || cfg->rng != BK_RNG_NUMPY_MT ||
         cfg->seats_share_stream)
-        return set_err(h, BK_EINVAL, "bk_arena_advance: needs ARENA, FRONTIER order, NUMPY_MT per-seat streams%s", "");
+        return set_err(h, BK_EINVAL, "%s: needs ARENA, FRONTIER order, NUMPY_MT per-seat streams", name);
     if (mem == BK_MEM_DEVICE && ((uintptr_t)rng_state & 15))
-        return set_err(h, BK_EINVAL, "bk_arena_advance: rng_state must be 16-byte aligned%s", "");
+        return set_err(h, BK_EINVAL, "%s: rng_state must be 16-byte aligned", name);
+    return BK_OK;
+}
+
+int bk_arena_advance(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const bk_rollout_cfg* cfg,
+                     const uint8_t* seat_masks, uint32_t* rng_state, bk_result* out, int mem) {
+    if (int rc = check_arena_call(h, "bk_arena_advance", states, sets, n, cfg, seat_masks, rng_state, out, mem)) return rc;
     if (n == 0) return BK_OK;
     return launch_playouts(h, states, n, nullptr, n, cfg, nullptr, out, states, mem, sets, sets, seat_masks,
                            rng_state);
@@ -7889,15 +8026,9 @@ int bk_arena_advance(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, co
 int bk_arena_step(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const bk_rollout_cfg* cfg,
                   const uint8_t* seat_masks, const uint8_t* quick_masks, const int32_t* forced, uint32_t* rng_state,
                   bk_result* out, bk_stop_info* stop_out, int mem) {
-    if (!h || !states || !sets || !cfg || !seat_masks || !rng_state || !out || n < 0)
-        return set_err(h, BK_EINVAL, "bk_arena_step: invalid arguments%s", "");
-    if (cfg->semantics != BK_SEM_ARENA || cfg->order != BK_ORDER_FRONTIER || cfg->rng != BK_RNG_NUMPY_MT ||
-        cfg->seats_share_stream)
-        return set_err(h, BK_EINVAL, "bk_arena_step: needs ARENA, FRONTIER order, NUMPY_MT per-seat streams%s", "");
+    if (int rc = check_arena_call(h, "bk_arena_step", states, sets, n, cfg, seat_masks, rng_state, out, mem)) return rc;
     if (quick_masks && !stop_out)
         return set_err(h, BK_EINVAL, "bk_arena_step: quick_masks goes with stop_out%s", "");
-    if (mem == BK_MEM_DEVICE && ((uintptr_t)rng_state & 15))
-        return set_err(h, BK_EINVAL, "bk_arena_step: rng_state must be 16-byte aligned%s", "");
     if (mem == BK_MEM_HOST && forced)
         for (int32_t i = 0; i < n; ++i)
             if (forced[i] < BK_FORCE_SKIP || (forced[i] >= 0 && !(forced[i] & BK_FORCE_INDEX) && forced[i] >= BK_NUM_ORIENTS * 400))
@@ -7912,8 +8043,7 @@ int bk_snap_plan_size(void) { return (int)sizeof(bk_snap_plan); }
 int bk_arena_step_snap(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const bk_rollout_cfg* cfg,
                        const uint8_t* seat_masks, const uint8_t* quick_masks, const int32_t* forced,
                        uint32_t* rng_state, bk_result* out, bk_stop_info* stop_out, const bk_snap_plan* plan, int mem) {
-    if (!h || !states || !sets || !cfg || !seat_masks || !rng_state || !out || n < 0)
-        return set_err(h, BK_EINVAL, "bk_arena_step_snap: invalid arguments%s", "");
+    if (int rc = check_arena_call(h, "bk_arena_step_snap", states, sets, n, cfg, seat_masks, rng_state, out, mem)) return rc;
     if (mem != BK_MEM_DEVICE)
         return set_err(h, BK_EINVAL, "bk_arena_step_snap: BK_MEM_DEVICE only (the slots persist across steps)%s", "");
     if (!plan || !plan->states || !plan->sets || !plan->turn)
@@ -7925,13 +8055,8 @@ int bk_arena_step_snap(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, 
         return set_err(h, BK_EINVAL, "bk_arena_step_snap: the ply mask is empty%s", "");
     if (plan->ply_mask[0] & 1u)
         return set_err(h, BK_EINVAL, "bk_arena_step_snap: ply 0 is not captured here (the caller fills that slot)%s", "");
-    if (cfg->semantics != BK_SEM_ARENA || cfg->order != BK_ORDER_FRONTIER || cfg->rng != BK_RNG_NUMPY_MT ||
-        cfg->seats_share_stream)
-        return set_err(h, BK_EINVAL, "bk_arena_step_snap: needs ARENA, FRONTIER order, NUMPY_MT per-seat streams%s", "");
     if (quick_masks && !stop_out)
         return set_err(h, BK_EINVAL, "bk_arena_step_snap: quick_masks goes with stop_out%s", "");
-    if ((uintptr_t)rng_state & 15)
-        return set_err(h, BK_EINVAL, "bk_arena_step_snap: rng_state must be 16-byte aligned%s", "");
     if (n == 0) return BK_OK;
     return launch_playouts(h, states, n, nullptr, n, cfg, nullptr, out, states, mem, sets, sets, seat_masks,
                            rng_state, quick_masks, forced, stop_out, plan);
@@ -8170,73 +8295,24 @@ int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const 
             int32_t n_zobrist, const int32_t* zobrist_index, uint32_t* mt_state, uint64_t* tt_keys,
             double* tt_vals, int32_t* tt_count, const double* log_table, int32_t log_len,
             bk_mcts_node* nodes, double* rewards, uint8_t* hit_flags, bk_mcts_out* out, int mem) {
-    if (!h || !cfg || n_games < 0 || (mem != BK_MEM_HOST && mem != BK_MEM_DEVICE))
-        return set_err(h, BK_EINVAL, "bk_mcts: invalid arguments%s", "");
+    MctsCall c{h, "bk_mcts", roots, root_sets, players, root_hash, n_games, cfg, zobrist, n_zobrist, zobrist_index,
+               tt_keys, tt_vals, tt_count, log_table, log_len, nodes, rewards, hit_flags, out, mem};
+    if (c.bad_args()) return set_err(h, BK_EINVAL, "bk_mcts: invalid arguments%s", "");
     if (n_games == 0) return BK_OK;
-    if (!roots || !root_sets || !players || !zobrist || n_zobrist < 1 || !zobrist_index ||
-        !mt_state || !log_table || log_len < 1 || !out || (rewards == nullptr) != (hit_flags == nullptr))
-        return set_err(h, BK_EINVAL, "bk_mcts: missing buffer%s", "");
-    if (cfg->iterations < 0 || cfg->max_rollout_moves <= 0 || cfg->node_cap < 1 || cfg->time_limit_us < 0 ||
-        cfg->iter_stop < 0 || (cfg->resume != 0 && cfg->resume != 1) ||
-        (cfg->rollout_policy != BK_MCTS_ROLLOUT_RANDOM && cfg->rollout_policy != BK_MCTS_ROLLOUT_HEURISTIC))
-        return set_err(h, BK_EINVAL, "bk_mcts: bad cfg (iterations/max_rollout_moves/node_cap/iter_stop/resume)%s", "");
-    if (cfg->resume && !nodes)
-        return set_err(h, BK_EINVAL, "bk_mcts: resume needs the caller's nodes buffer%s", "");
+    int rc = c.check_buffers(!mt_state, cfg->max_rollout_moves <= 0 ||
+                             (cfg->rollout_policy != BK_MCTS_ROLLOUT_RANDOM && cfg->rollout_policy != BK_MCTS_ROLLOUT_HEURISTIC),
+                             "bk_mcts: bad cfg (iterations/max_rollout_moves/node_cap/iter_stop/resume)%s");
+    if (rc) return rc;
     if ((cfg->flags & BK_MCTS_STATE_ROWS) && mem != BK_MEM_DEVICE)
         return set_err(h, BK_EINVAL, "bk_mcts: BK_MCTS_STATE_ROWS needs BK_MEM_DEVICE buffers%s", "");
-    if (cfg->use_tt && (!tt_keys || !tt_vals || !tt_count || cfg->tt_cap < 2 || (cfg->tt_cap & (cfg->tt_cap - 1))))
-        return set_err(h, BK_EINVAL, "bk_mcts: use_tt needs tt buffers and a power-of-two tt_cap%s", "");
-    if (mem == BK_MEM_HOST) {
-        for (int32_t g = 0; g < n_games; ++g) {
-            if (players[g] > 3 || zobrist_index[g] < 0 || zobrist_index[g] >= n_zobrist || mt_state[(size_t)g * 625 + 624] > 624)
-                return set_err(h, BK_EINVAL, "bk_mcts: bad player / zobrist_index / mt pos%s", "");
-            for (int q = 0; q < 4; ++q)
-                if (root_sets[g].mask[q] + 1u > BK_FSET_SLOTS)
-                    return set_err(h, BK_EINVAL, "bk_mcts: root frontier table too large%s", "");
-            if (cfg->use_tt && (tt_count[g] < 0 || tt_count[g] >= cfg->tt_cap))
-                return set_err(h, BK_EINVAL, "bk_mcts: bad tt_count%s", "");
-        }
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    BK_IDLE(h, "bk_mcts");
-    const size_t n = (size_t)n_games, ttc = cfg->use_tt ? (size_t)cfg->tt_cap : 0;
-    const size_t it = (size_t)cfg->iterations;
-    const int io = cfg->resume ? Staging::INOUT : Staging::OUT;  // a resumed search reads what the last one left
-    const size_t node_bytes = sizeof(bk_mcts_node) * (size_t)cfg->node_cap * n;
-    Staging st(h, mem);
-    const auto s_roots = st.in(roots, sizeof(bk_state) * n);
-    const auto s_sets = st.in(root_sets, sizeof(bk_fset) * n);
-    const auto s_players = st.in(players, n);
-    const auto s_hash = st.in(root_hash, sizeof(uint64_t) * n);
-    const auto s_zob = st.in(zobrist, sizeof(uint64_t) * MC_ZOB * (size_t)n_zobrist);
-    const auto s_zidx = st.in(zobrist_index, sizeof(int32_t) * n);
-    const auto s_mt = st.inout(mt_state, sizeof(uint32_t) * 625 * n);
-    const auto s_ttk = st.inout(tt_keys, sizeof(uint64_t) * ttc * n);
-    const auto s_ttv = st.inout(tt_vals, sizeof(double) * ttc * n);
-    const auto s_ttn = st.inout(tt_count, cfg->use_tt ? sizeof(int32_t) * n : 0);
-    const auto s_log = st.in(log_table, sizeof(double) * (size_t)log_len);
-    const auto s_nodes = st.add(nodes, node_bytes, io);
-    const auto s_rewards = st.add(rewards, sizeof(double) * it * n, io);
-    const auto s_hits = st.add(hit_flags, it * n, io);
-    const auto s_out = st.add(out, sizeof(bk_mcts_out) * n, io);
-    int rc = st.commit();
+    rc = c.check_games([&](int32_t g) { return mt_state[(size_t)g * 625 + 624] > 624; },
+                       "bk_mcts: bad player / zobrist_index / mt pos%s");
     if (rc) return rc;
+    if ((rc = c.stage())) return rc;
+    const size_t n = (size_t)n_games;
+    const auto s_mt = c.st.inout(mt_state, sizeof(uint32_t) * 625 * n);
+    if ((rc = c.commit())) return rc;
     Buf* const wb = h->buf;  // the work buffers, by bk_handle_s's names
-    bk_mcts_node* d_nodes = s_nodes.dev();
-    if (!nodes) {  // no caller's pool: the handle's, in either memory mode
-        rc = grow(h, wb[bk_handle_s::NODES], node_bytes);
-        if (rc) return rc;
-        d_nodes = (bk_mcts_node*)wb[bk_handle_s::NODES].p;
-    }
-    const uint64_t* d_hash = s_hash.dev();
-    if (!root_hash) {  // ZobristHash.hash_board of every root, on the device (untimed)
-        rc = grow(h, wb[bk_handle_s::RH], sizeof(uint64_t) * n);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_root_hash, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->cur,
-                           s_roots.dev(), s_zob.dev(), s_zidx.dev(), (uint64_t*)wb[bk_handle_s::RH].p, n_games);
-        HIPCHK(h, hipGetLastError());
-        d_hash = (const uint64_t*)wb[bk_handle_s::RH].p;
-    }
     // persistent grid: every resident slot pulls whole searches from the counter
     const bool heur = cfg->rollout_policy == BK_MCTS_ROLLOUT_HEURISTIC;
     // one wave per search (k_mcts_coop) when the batch cannot fill the chip with one
@@ -8270,22 +8346,16 @@ int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const 
     if (rc) return rc;
     rc = grow(h, wb[bk_handle_s::MCLANE], sizeof(McLane) * (size_t)nslots);
     if (rc) return rc;
-    int khz = 0;
-    HIPCHK(h, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->device));
-    if (khz <= 0) khz = 100000;
-    HIPCHK(h, hipMemsetAsync(h->d_counter, 0, 2 * sizeof(uint32_t), h->cur));  // [2] is sticky
     const uint64_t per_lane = ((uint64_t)n_games * spread + nslots - 1) / nslots + 1;
     // a waiting lane waits at most one simulation of the others (2x)
     const uint64_t steps = 2 * per_lane * ((uint64_t)cfg->iterations + 1) * ((uint64_t)cfg->max_rollout_moves + 2) + 64;
     int32_t tree_batch = MC_TREE_BATCH;
     tree_batch = (int32_t)tune_or(h, BK_TUNE_TREE_BATCH, tree_batch);
     if (tree_batch < 1) tree_batch = 1;
-    MctsArgs a{s_roots.dev(), s_sets.dev(), s_players.dev(), d_hash, n_games, *cfg, s_zob.dev(), s_zidx.dev(),
-               s_mt.dev(), s_ttk.dev(), s_ttv.dev(), s_ttn.dev(), s_log.dev(), log_len, d_nodes, s_rewards.dev(),
-               s_hits.dev(), s_out.dev(), (uint32_t*)wb[bk_handle_s::SLAB].p, (McLane*)wb[bk_handle_s::MCLANE].p,
-               h->d_counter, steps, (uint64_t)cfg->time_limit_us * (uint64_t)khz / 1000u, tree_batch, spread, 1, 1};
-    a.diag = h->d_diag;
-    a.launch_seq = ++h->mcts_launches;
+    MctsArgs a{c.s_roots.dev(), c.s_sets.dev(), c.s_players.dev(), c.d_hash, n_games, *cfg, c.s_zob.dev(),
+               c.s_zidx.dev(), s_mt.dev(), c.s_ttk.dev(), c.s_ttv.dev(), c.s_ttn.dev(), c.s_log.dev(), log_len,
+               c.d_nodes, c.s_rewards.dev(), c.s_hits.dev(), c.s_out.dev(), (uint32_t*)wb[bk_handle_s::SLAB].p,
+               (McLane*)wb[bk_handle_s::MCLANE].p, h->d_counter, steps, c.time_ticks, tree_batch, spread, 1, 1};
     a.state_rows = (cfg->flags & BK_MCTS_STATE_ROWS) ? 1 : 0;
     a.done = h->mcts_done;
     if (a.state_rows) {  // the searches work on copies of their agents' MT rows
@@ -8294,14 +8364,7 @@ int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const 
         a.mt_rows = a.mt;
         a.mt = (uint32_t*)wb[bk_handle_s::MTWORK].p;
     }
-    {
-        const size_t sb = sizeof(uint32_t) * (((size_t)n_games + 31) / 32 + 1);
-        rc = grow(h, wb[bk_handle_s::STARTED], sb);
-        if (rc) return rc;
-        a.started = (uint32_t*)wb[bk_handle_s::STARTED].p;
-        HIPCHK(h, hipMemsetAsync(a.started, 0, sb, h->cur));
-    }
-    a.coop_walk = (int)tune_or(h, BK_TUNE_COOP_WALK, a.coop_walk);
+    if ((rc = c.arm(a))) return rc;
     a.coop_balanced = (int)tune_or(h, BK_TUNE_COOP_BAL, a.coop_balanced);
     // spread 2: the idle odd lane of each pair splits the even lane's stencil (k_mcts_pair)
     const bool pair = tune_or(h, BK_TUNE_MCTS_PAIR, 1) != 0;
@@ -8325,8 +8388,7 @@ int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const 
         h->busy_stream = h->cur;
         return BK_OK;
     }
-    rc = finish_guarded(h, st, BK_STICKY_GUARD, BK_EOVERFLOW, "bk_mcts: step guard tripped%s");
-    return rc ? rc : take_diag(h);  // a search broke a tree invariant (mc_diag)
+    return c.finish("bk_mcts: step guard tripped%s");
 }
 
 int bk_mcts_learned(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const uint8_t* players,
@@ -8335,81 +8397,26 @@ int bk_mcts_learned(bk_handle h, const bk_state* roots, const bk_fset* root_sets
                     int32_t* tt_count, const double* log_table, int32_t log_len, const bk_winprob_model* model,
                     int32_t max_turns, double bias_weight, double* prior_bias, int32_t* bias_updates,
                     bk_mcts_node* nodes, double* rewards, uint8_t* hit_flags, bk_mcts_out* out, int mem) {
-    if (!h || !cfg || !model || n_games < 0 || (mem != BK_MEM_HOST && mem != BK_MEM_DEVICE))
-        return set_err(h, BK_EINVAL, "bk_mcts_learned: invalid arguments%s", "");
+    MctsCall c{h, "bk_mcts_learned", roots, root_sets, players, root_hash, n_games, cfg, zobrist, n_zobrist,
+               zobrist_index, tt_keys, tt_vals, tt_count, log_table, log_len, nodes, rewards, hit_flags, out, mem};
+    if (c.bad_args() || !model) return set_err(h, BK_EINVAL, "bk_mcts_learned: invalid arguments%s", "");
+    // the model, the weight and max_turns are judged before anything else, an empty batch included
     if (!__builtin_isfinite(model->intercept) || !__builtin_isfinite(bias_weight))
         return set_err(h, BK_EINVAL, "bk_mcts_learned: the model's intercept or the bias weight is not finite%s", "");
-    for (int k = 0; k < BK_SNAPSHOT_COLUMNS; ++k) {
-        if (!__builtin_isfinite(model->mean[k]) || !__builtin_isfinite(model->scale[k]) ||
-            !__builtin_isfinite(model->coef[k]))
-            return set_err(h, BK_EINVAL, "bk_mcts_learned: the model has a non-finite mean, scale or coef%s", "");
-        if (model->scale[k] == 0.0)
-            return set_err(h, BK_EINVAL, "bk_mcts_learned: the model has a scale of 0%s", "");
-    }
+    int rc = check_winprob_model(h, "bk_mcts_learned", model);
+    if (rc) return rc;
     if (max_turns < 0) return set_err(h, BK_EINVAL, "bk_mcts_learned: max_turns must be >= 0%s", "");
     if (n_games == 0) return BK_OK;
-    if (!roots || !root_sets || !players || !zobrist || n_zobrist < 1 || !zobrist_index || !log_table || log_len < 1 ||
-        !out || !bias_updates || (rewards == nullptr) != (hit_flags == nullptr) || (bias_weight != 0.0 && !prior_bias))
-        return set_err(h, BK_EINVAL, "bk_mcts_learned: missing buffer%s", "");
-    if (cfg->iterations < 0 || cfg->node_cap < 1 || cfg->time_limit_us < 0 || cfg->iter_stop < 0 ||
-        (cfg->resume != 0 && cfg->resume != 1) || cfg->flags != 0)
-        return set_err(h, BK_EINVAL, "bk_mcts_learned: bad cfg (iterations/node_cap/iter_stop/resume; flags must be 0)%s", "");
-    if (cfg->resume && !nodes)
-        return set_err(h, BK_EINVAL, "bk_mcts_learned: resume needs the caller's nodes buffer%s", "");
-    if (cfg->use_tt && (!tt_keys || !tt_vals || !tt_count || cfg->tt_cap < 2 || (cfg->tt_cap & (cfg->tt_cap - 1))))
-        return set_err(h, BK_EINVAL, "bk_mcts_learned: use_tt needs tt buffers and a power-of-two tt_cap%s", "");
-    if (mem == BK_MEM_HOST) {
-        for (int32_t g = 0; g < n_games; ++g) {
-            if (players[g] > 3 || zobrist_index[g] < 0 || zobrist_index[g] >= n_zobrist)
-                return set_err(h, BK_EINVAL, "bk_mcts_learned: bad player / zobrist_index%s", "");
-            for (int q = 0; q < 4; ++q)
-                if (root_sets[g].mask[q] + 1u > BK_FSET_SLOTS)
-                    return set_err(h, BK_EINVAL, "bk_mcts_learned: root frontier table too large%s", "");
-            if (cfg->use_tt && (tt_count[g] < 0 || tt_count[g] >= cfg->tt_cap))
-                return set_err(h, BK_EINVAL, "bk_mcts_learned: bad tt_count%s", "");
-        }
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    BK_IDLE(h, "bk_mcts_learned");
-    const size_t n = (size_t)n_games, ttc = cfg->use_tt ? (size_t)cfg->tt_cap : 0;
-    const size_t it = (size_t)cfg->iterations;
-    const int io = cfg->resume ? Staging::INOUT : Staging::OUT;  // a resumed search reads what the last one left
-    const size_t node_bytes = sizeof(bk_mcts_node) * (size_t)cfg->node_cap * n;
-    Staging st(h, mem);
-    const auto s_roots = st.in(roots, sizeof(bk_state) * n);
-    const auto s_sets = st.in(root_sets, sizeof(bk_fset) * n);
-    const auto s_players = st.in(players, n);
-    const auto s_hash = st.in(root_hash, sizeof(uint64_t) * n);
-    const auto s_zob = st.in(zobrist, sizeof(uint64_t) * MC_ZOB * (size_t)n_zobrist);
-    const auto s_zidx = st.in(zobrist_index, sizeof(int32_t) * n);
-    const auto s_ttk = st.inout(tt_keys, sizeof(uint64_t) * ttc * n);
-    const auto s_ttv = st.inout(tt_vals, sizeof(double) * ttc * n);
-    const auto s_ttn = st.inout(tt_count, cfg->use_tt ? sizeof(int32_t) * n : 0);
-    const auto s_log = st.in(log_table, sizeof(double) * (size_t)log_len);
-    const auto s_nodes = st.add(nodes, node_bytes, io);
-    const auto s_prior = st.add(bias_weight != 0.0 ? prior_bias : nullptr, sizeof(double) * (size_t)cfg->node_cap * n, io);
-    const auto s_bias = st.add(bias_updates, sizeof(int32_t) * n, io);
-    const auto s_rewards = st.add(rewards, sizeof(double) * it * n, io);
-    const auto s_hits = st.add(hit_flags, it * n, io);
-    const auto s_out = st.add(out, sizeof(bk_mcts_out) * n, io);
-    int rc = st.commit();
+    rc = c.check_buffers(!bias_updates || (bias_weight != 0.0 && !prior_bias), cfg->flags != 0,
+                         "bk_mcts_learned: bad cfg (iterations/node_cap/iter_stop/resume; flags must be 0)%s");
     if (rc) return rc;
-    Buf* const wb = h->buf;
-    bk_mcts_node* d_nodes = s_nodes.dev();
-    if (!nodes) {  // no caller's pool: the handle's, in either memory mode
-        rc = grow(h, wb[bk_handle_s::NODES], node_bytes);
-        if (rc) return rc;
-        d_nodes = (bk_mcts_node*)wb[bk_handle_s::NODES].p;
-    }
-    const uint64_t* d_hash = s_hash.dev();
-    if (!root_hash) {  // ZobristHash.hash_board of every root, on the device (untimed)
-        rc = grow(h, wb[bk_handle_s::RH], sizeof(uint64_t) * n);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_root_hash, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, h->cur,
-                           s_roots.dev(), s_zob.dev(), s_zidx.dev(), (uint64_t*)wb[bk_handle_s::RH].p, n_games);
-        HIPCHK(h, hipGetLastError());
-        d_hash = (const uint64_t*)wb[bk_handle_s::RH].p;
-    }
+    rc = c.check_games([](int32_t) { return false; }, "bk_mcts_learned: bad player / zobrist_index%s");
+    if (rc) return rc;
+    if ((rc = c.stage())) return rc;
+    const size_t n = (size_t)n_games;
+    const auto s_prior = c.st.add(bias_weight != 0.0 ? prior_bias : nullptr, sizeof(double) * (size_t)cfg->node_cap * n, c.io);
+    const auto s_bias = c.st.add(bias_updates, sizeof(int32_t) * n, c.io);
+    if ((rc = c.commit())) return rc;
     // persistent grid of COOP_WAVES-search blocks; the search's McLane and slab live in LDS
     // (DESIGN.md 4 has the kernel's resources)
     int coop_bpc = 3;  // by LDS: 48 KB per block
@@ -8419,36 +8426,22 @@ int bk_mcts_learned(bk_handle h, const bk_state* roots, const bk_fset* root_sets
     if (blocks > need) blocks = need;
     if (blocks < 1) blocks = 1;
     const uint32_t nslots = (uint32_t)blocks * COOP_WAVES;
-    int khz = 0;
-    HIPCHK(h, hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->device));
-    if (khz <= 0) khz = 100000;
-    HIPCHK(h, hipMemsetAsync(h->d_counter, 0, 2 * sizeof(uint32_t), h->cur));  // [2] is sticky
     const uint64_t per_wave = ((uint64_t)n_games + nslots - 1) / nslots + 1;
     const uint64_t steps = 2 * per_wave * ((uint64_t)cfg->iterations + 1) * 3 + 64;  // one movegen per iteration
     bk_mcts_cfg kcfg = *cfg;
     kcfg.max_rollout_moves = 1;  // (unused: no rollout)
     kcfg.rollout_policy = BK_MCTS_ROLLOUT_RANDOM;
-    MctsArgs a{s_roots.dev(), s_sets.dev(), s_players.dev(), d_hash, n_games, kcfg, s_zob.dev(), s_zidx.dev(),
-               nullptr, s_ttk.dev(), s_ttv.dev(), s_ttn.dev(), s_log.dev(), log_len, d_nodes, s_rewards.dev(),
-               s_hits.dev(), s_out.dev(), nullptr, nullptr,
-               h->d_counter, steps, (uint64_t)cfg->time_limit_us * (uint64_t)khz / 1000u, MC_TREE_BATCH, 1, 1, 1};
-    a.diag = h->d_diag;
-    a.launch_seq = ++h->mcts_launches;
+    MctsArgs a{c.s_roots.dev(), c.s_sets.dev(), c.s_players.dev(), c.d_hash, n_games, kcfg, c.s_zob.dev(),
+               c.s_zidx.dev(), nullptr, c.s_ttk.dev(), c.s_ttv.dev(), c.s_ttn.dev(), c.s_log.dev(), log_len,
+               c.d_nodes, c.s_rewards.dev(), c.s_hits.dev(), c.s_out.dev(), nullptr, nullptr,
+               h->d_counter, steps, c.time_ticks, MC_TREE_BATCH, 1, 1, 1};
     a.state_rows = 0;
     a.done = nullptr;
-    {
-        const size_t sb = sizeof(uint32_t) * (((size_t)n_games + 31) / 32 + 1);
-        rc = grow(h, wb[bk_handle_s::STARTED], sb);
-        if (rc) return rc;
-        a.started = (uint32_t*)wb[bk_handle_s::STARTED].p;
-        HIPCHK(h, hipMemsetAsync(a.started, 0, sb, h->cur));
-    }
-    a.coop_walk = (int)tune_or(h, BK_TUNE_COOP_WALK, a.coop_walk);
+    if ((rc = c.arm(a))) return rc;
     a.kernel_id = BK_DIAG_K_COOP_L;
     LeafArgs la{*model, max_turns, bias_weight, s_prior.dev(), s_bias.dev()};
     BK_LAUNCH(h, k_mcts_coop_l, dim3(blocks), dim3(COOP_WAVES * WAVE), a, la);
-    rc = finish_guarded(h, st, BK_STICKY_GUARD, BK_EOVERFLOW, "bk_mcts_learned: step guard tripped%s");
-    return rc ? rc : take_diag(h);  // a search broke a tree invariant (mc_diag)
+    return c.finish("bk_mcts_learned: step guard tripped%s");
 }
 
 }  // extern "C"

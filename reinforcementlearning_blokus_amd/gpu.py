@@ -667,32 +667,15 @@ class BlokusGPU:
         (memory the device can write; `out` is then ignored)."""
         import torch
         n = roots.shape[0]
-        use_tt = tt_keys is not None
-        node_cap = nodes.shape[1] // N.MCTS_NODE_DTYPE.itemsize
         rows = mt_state.shape[0] if state_rows else n  # agent rows, or one per search
         if state_rows and rows < zobrist.shape[0]:  # zobrist_index < n_zobrist: every row it names exists
             raise ValueError(f"state_rows: {rows} mt_state rows for {zobrist.shape[0]} zobrist rows")
-        tensors = dict(roots=(roots, torch.uint8, (n, 256)), root_sets=(root_sets, torch.uint8, (n, N.FSET_DTYPE.itemsize)),
-                       players=(players, torch.uint8, (n,)),
-                       zobrist_index=(zobrist_index, torch.int32, (n,)), mt_state=(mt_state, torch.int32, (rows, 625)),
-                       nodes=(nodes, torch.uint8, (n, node_cap * N.MCTS_NODE_DTYPE.itemsize)))
-        if out_ptr is None:
-            tensors.update(out=(out, torch.uint8, (n, N.MCTS_OUT_DTYPE.itemsize)))
-        else:
+        if out_ptr is not None:
             assert asynchronous and not (chunk or stop_after or resume_from), "out_ptr: one asynchronous launch"
-        if root_hash is not None:  # None: ZobristHash.hash_board computed on the device (k_root_hash)
-            tensors.update(root_hash=(root_hash, torch.int64, (n,)))
-        if use_tt:
-            cap = tt_keys.shape[1]
-            tensors.update(tt_keys=(tt_keys, torch.int64, (rows, cap)), tt_vals=(tt_vals, torch.float64, (rows, cap)),
-                           tt_count=(tt_count, torch.int32, (rows,)))
-        if rewards is not None:
-            tensors.update(rewards=(rewards, torch.float64, (n, iterations)),
-                           hit_flags=(hit_flags, torch.uint8, (n, iterations)))
-        for name, (t, dt, shape) in tensors.items():
-            _check_device_tensor(t, name, dt, shape, self.device)
-        _check_device_tensor(zobrist, "zobrist", torch.int64, (zobrist.shape[0], N.MCTS_ZOBRIST_WORDS), self.device)
-        _check_device_tensor(log_table, "log_table", torch.float64, (log_table.shape[0],), self.device)
+        node_cap = self._check_search_tensors(
+            n, iterations, rows, roots, root_sets, players, root_hash, zobrist, zobrist_index, log_table, nodes,
+            out if out_ptr is None else None, tt_keys, tt_vals, tt_count, rewards, hit_flags,
+            mt_state=(mt_state, torch.int32, (rows, 625)))
         self._stream_from_torch()
         d = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
         assert not ((chunk or stop_after or resume_from) and time_limit_us), "timed searches run in one launch"
@@ -701,12 +684,9 @@ class BlokusGPU:
             stops = [x for x in stops if 0 < x < stop_after] + [stop_after]
         if resume_from is not None:  # continue searches a stop_after call left at resume_from
             stops = [x for x in stops if x == 0 or x > resume_from]
-        for j, stop in enumerate(stops):
-            resume = int(j > 0 or resume_from is not None)
-            cfg = N.BkMctsCfg(iterations, max_rollout_moves, float(exploration), int(use_tt), node_cap,
-                              tt_keys.shape[1] if use_tt else 0, int(time_limit_us), stop, resume,
-                              int(rollout_policy), (N.MCTS_ASYNC if asynchronous else 0) |
-                              (N.MCTS_STATE_ROWS if state_rows else 0))
+        flags = (N.MCTS_ASYNC if asynchronous else 0) | (N.MCTS_STATE_ROWS if state_rows else 0)
+        for stop, cfg in _search_cfgs(stops, resume_from is not None, iterations, max_rollout_moves, exploration,
+                                      tt_keys, node_cap, time_limit_us, rollout_policy, flags):
             self.handle.mcts(d(roots), d(root_sets), d(players), d(root_hash), n, cfg, d(zobrist), zobrist.shape[0],
                              d(zobrist_index), d(mt_state), d(tt_keys), d(tt_vals), d(tt_count), d(log_table),
                              log_table.shape[0], d(nodes), d(rewards), d(hit_flags),
@@ -716,11 +696,7 @@ class BlokusGPU:
         if asynchronous:
             assert len(stops) == 1, "an asynchronous search is one launch"
             return
-        st = out.view(torch.int32)[:, 6] & ~N.MCTS_EUNCERT
-        bad = int((st != 0).sum().item())
-        if bad:
-            raise RuntimeError(f"bk_mcts: {bad} searches stopped early, status bits "
-                               f"{sorted(set(st[st != 0].tolist()))[:8]}")
+        _raise_stopped_early("bk_mcts", out, ignore=N.MCTS_EUNCERT)
 
     def mcts_learned_device(self, roots, root_sets, players, root_hash, zobrist, zobrist_index, log_table, nodes, out,
                             model, bias_updates, *, iterations: int, max_turns: int, bias_weight: float = 0.0,
@@ -735,49 +711,55 @@ class BlokusGPU:
         check=False leaves the status words in `out` to the caller instead of raising."""
         import torch
         n = roots.shape[0]
-        use_tt = tt_keys is not None
-        node_cap = nodes.shape[1] // N.MCTS_NODE_DTYPE.itemsize
         native = model.as_native() if hasattr(model, "as_native") else model
-        tensors = dict(roots=(roots, torch.uint8, (n, 256)), root_sets=(root_sets, torch.uint8, (n, N.FSET_DTYPE.itemsize)),
-                       players=(players, torch.uint8, (n,)), zobrist_index=(zobrist_index, torch.int32, (n,)),
-                       nodes=(nodes, torch.uint8, (n, node_cap * N.MCTS_NODE_DTYPE.itemsize)),
-                       out=(out, torch.uint8, (n, N.MCTS_OUT_DTYPE.itemsize)),
-                       bias_updates=(bias_updates, torch.int32, (n,)))
-        if root_hash is not None:
-            tensors.update(root_hash=(root_hash, torch.int64, (n,)))
+        own = dict(bias_updates=(bias_updates, torch.int32, (n,)))
         if bias_weight != 0.0:
             if prior_bias is None:
                 raise ValueError("mcts_learned_device: a bias weight needs the prior_bias tensor")
-            tensors.update(prior_bias=(prior_bias, torch.float64, (n, node_cap)))
-        if use_tt:
-            cap = tt_keys.shape[1]
-            tensors.update(tt_keys=(tt_keys, torch.int64, (n, cap)), tt_vals=(tt_vals, torch.float64, (n, cap)),
-                           tt_count=(tt_count, torch.int32, (n,)))
-        if rewards is not None:
-            tensors.update(rewards=(rewards, torch.float64, (n, iterations)),
-                           hit_flags=(hit_flags, torch.uint8, (n, iterations)))
-        for name, (t, dt, shape) in tensors.items():
-            _check_device_tensor(t, name, dt, shape, self.device)
-        _check_device_tensor(zobrist, "zobrist", torch.int64, (zobrist.shape[0], N.MCTS_ZOBRIST_WORDS), self.device)
-        _check_device_tensor(log_table, "log_table", torch.float64, (log_table.shape[0],), self.device)
+            own.update(prior_bias=(prior_bias, torch.float64, (n, nodes.shape[1] // N.MCTS_NODE_DTYPE.itemsize)))
+        node_cap = self._check_search_tensors(n, iterations, n, roots, root_sets, players, root_hash, zobrist,
+                                              zobrist_index, log_table, nodes, out, tt_keys, tt_vals, tt_count,
+                                              rewards, hit_flags, **own)
         self._stream_from_torch()
         d = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
         assert not (chunk and time_limit_us), "timed searches run in one launch"
-        for j, stop in enumerate(mcts_chunks(iterations, chunk)):
-            cfg = N.BkMctsCfg(iterations, 1, float(exploration), int(use_tt), node_cap,
-                              tt_keys.shape[1] if use_tt else 0, int(time_limit_us), stop, int(j > 0), 0, 0)
+        for _, cfg in _search_cfgs(mcts_chunks(iterations, chunk), False, iterations, 1, exploration, tt_keys,
+                                   node_cap, time_limit_us, 0, 0):
             self.handle.mcts_learned(d(roots), d(root_sets), d(players), d(root_hash), n, cfg, d(zobrist),
                                      zobrist.shape[0], d(zobrist_index), d(tt_keys), d(tt_vals), d(tt_count),
                                      d(log_table), log_table.shape[0], native, max_turns, bias_weight,
                                      d(prior_bias) if bias_weight != 0.0 else 0, d(bias_updates), d(nodes),
                                      d(rewards), d(hit_flags), d(out), N.MEM_DEVICE)
-        if not check:
-            return
-        st = out.view(torch.int32)[:, 6]
-        bad = int((st != 0).sum().item())
-        if bad:
-            raise RuntimeError(f"bk_mcts_learned: {bad} searches stopped early, status bits "
-                               f"{sorted(set(st[st != 0].tolist()))[:8]}")
+        if check:
+            _raise_stopped_early("bk_mcts_learned", out)
+
+    def _check_search_tensors(self, n, iterations, tt_rows, roots, root_sets, players, root_hash, zobrist,
+                              zobrist_index, log_table, nodes, out, tt_keys, tt_vals, tt_count, rewards, hit_flags,
+                              **own):
+        """_check_device_tensor on the buffers mcts_device and mcts_learned_device both take
+        (root_hash, out, the TT triple and rewards / hit_flags may be absent) and on the
+        caller's `own` {name: (tensor, dtype, shape)}.  Returns nodes' node_cap."""
+        import torch
+        node_cap = nodes.shape[1] // N.MCTS_NODE_DTYPE.itemsize
+        tensors = dict(roots=(roots, torch.uint8, (n, 256)), root_sets=(root_sets, torch.uint8, (n, N.FSET_DTYPE.itemsize)),
+                       players=(players, torch.uint8, (n,)), zobrist_index=(zobrist_index, torch.int32, (n,)),
+                       nodes=(nodes, torch.uint8, (n, node_cap * N.MCTS_NODE_DTYPE.itemsize)), **own)
+        if out is not None:
+            tensors.update(out=(out, torch.uint8, (n, N.MCTS_OUT_DTYPE.itemsize)))
+        if root_hash is not None:  # None: ZobristHash.hash_board computed on the device (k_root_hash)
+            tensors.update(root_hash=(root_hash, torch.int64, (n,)))
+        if tt_keys is not None:
+            cap = tt_keys.shape[1]
+            tensors.update(tt_keys=(tt_keys, torch.int64, (tt_rows, cap)), tt_vals=(tt_vals, torch.float64, (tt_rows, cap)),
+                           tt_count=(tt_count, torch.int32, (tt_rows,)))
+        if rewards is not None:
+            tensors.update(rewards=(rewards, torch.float64, (n, iterations)),
+                           hit_flags=(hit_flags, torch.uint8, (n, iterations)))
+        tensors.update(zobrist=(zobrist, torch.int64, (zobrist.shape[0], N.MCTS_ZOBRIST_WORDS)),
+                       log_table=(log_table, torch.float64, (log_table.shape[0],)))
+        for name, (t, dt, shape) in tensors.items():
+            _check_device_tensor(t, name, dt, shape, self.device)
+        return node_cap
 
 
 class SnapSlots:
@@ -827,6 +809,27 @@ def _check_device_tensor(t, name, dtype, shape, device):
         raise ValueError(f"{name}: expected {dtype} {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
     if not t.is_contiguous():
         raise ValueError(f"{name}: must be contiguous")
+
+
+def _search_cfgs(stops, resumed, iterations, max_rollout_moves, exploration, tt_keys, node_cap, time_limit_us,
+                 rollout_policy, flags):
+    """(stop, BkMctsCfg) for each launch of a search split at `stops` (mcts_chunks): every
+    launch after the first resumes, and the first too when `resumed`."""
+    use_tt = tt_keys is not None
+    for j, stop in enumerate(stops):
+        yield stop, N.BkMctsCfg(iterations, max_rollout_moves, float(exploration), int(use_tt), node_cap,
+                                tt_keys.shape[1] if use_tt else 0, int(time_limit_us), stop, int(j > 0 or resumed),
+                                int(rollout_policy), flags)
+
+
+def _raise_stopped_early(name, out, ignore: int = 0):
+    """Raise if a search of entry point `name` left status bits outside `ignore` in its out record."""
+    import torch
+    st = out.view(torch.int32)[:, 6] & ~ignore
+    bad = int((st != 0).sum().item())
+    if bad:
+        raise RuntimeError(f"{name}: {bad} searches stopped early, status bits "
+                           f"{sorted(set(st[st != 0].tolist()))[:8]}")
 
 
 def mcts_node_cap(iterations: int) -> int:

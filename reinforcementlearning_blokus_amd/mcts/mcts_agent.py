@@ -45,6 +45,7 @@ searches of ``search`` and ``kernel`` do not evaluate leaves and reject these op
 from __future__ import annotations
 
 import contextlib
+import functools
 import math
 import time
 import warnings
@@ -92,11 +93,12 @@ def _tt_scatter(ags, pool, rows, tk, tv, tc):
         a._gpu_tt.count[0] = cnt
 
 
-def _leaf_search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, iters, c, use_tt, tl_us, model, max_turns, bias_w):
-    """One bk_mcts_learned launch for search_packed's leaf agents, every buffer in HBM; the
-    TT rows as in _search_on_device.  Returns dict(out, rewards, hit_flags, bias_updates,
-    children): children[j] = the root's children of search j as [move, visits, total,
-    prior_bias] in expansion order."""
+def _search_on_device(gpu, ags, launch, rts, sts, pl, rh, zob, zidx, iters, c, use_tt, tl_us):
+    """One search launch for search_packed with every buffer in HBM (BK_MEM_DEVICE): `launch`
+    is gpu.mcts_device or gpu.mcts_learned_device with its own arguments bound.  The agents'
+    TTs stay on the device between calls (TTPool rows, gathered into the launch's [n, cap]
+    block and scattered back); only the roots and per-search outputs cross PCIe.  Returns
+    dict(out, rewards, hit_flags) as host arrays and nodes, the node pools on the device."""
     import torch
 
     from .. import _native as N
@@ -107,26 +109,46 @@ def _leaf_search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, iters, c, use_
     lts = gpu.__dict__.setdefault("_log_tables", {})
     if iters not in lts:
         lts[iters] = up(mcts_log_table(iters))
-    cap_nodes = mcts_node_cap(iters)
     d_out = torch.zeros((n, N.MCTS_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
     d_rew = torch.empty((n, iters), dtype=torch.float64, device=dev)
     d_flags = torch.empty((n, iters), dtype=torch.uint8, device=dev)
-    d_nodes = torch.empty((n, cap_nodes * N.MCTS_NODE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-    d_prior = torch.zeros((n, cap_nodes), dtype=torch.float64, device=dev) if bias_w != 0.0 else None
-    d_bias = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_nodes = torch.empty((n, mcts_node_cap(iters) * N.MCTS_NODE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
     tk = tv = tc = None
+    # TT_LOCK from the rows' lease / gather to their scatter (synchronized by the count
+    # copy): another thread's search or pool growth cannot interleave (gpu.TT_LOCK)
     with (TT_LOCK if use_tt else contextlib.nullcontext()):
         if use_tt:
             pool, rows, tk, tv, tc = _tt_gather(gpu, ags, iters, dev)
-        gpu.mcts_learned_device(up(rts.view(np.uint8).reshape(n, 256)), up(sts.view(np.uint8).reshape(n, -1)), up(pl),
-                                up(rh.view(np.int64)), up(zob.view(np.int64)), up(zidx), lts[iters], d_nodes, d_out,
-                                model, d_bias, iterations=iters, max_turns=max_turns, bias_weight=bias_w,
-                                prior_bias=d_prior, tt_keys=tk, tt_vals=tv, tt_count=tc, rewards=d_rew,
-                                hit_flags=d_flags, exploration=c, time_limit_us=tl_us)
+        launch(roots=up(rts.view(np.uint8).reshape(n, 256)), root_sets=up(sts.view(np.uint8).reshape(n, -1)),
+               players=up(pl), root_hash=up(rh.view(np.int64)), zobrist=up(zob.view(np.int64)), zobrist_index=up(zidx),
+               log_table=lts[iters], nodes=d_nodes, out=d_out, iterations=iters, tt_keys=tk, tt_vals=tv, tt_count=tc,
+               rewards=d_rew, hit_flags=d_flags, exploration=c, time_limit_us=tl_us)
         if use_tt:
-            _tt_scatter(ags, pool, rows, tk, tv, tc)
+            _tt_scatter(ags, pool, rows, tk, tv, tc)  # synchronizes this stream
     out = d_out.cpu().numpy().view(N.MCTS_OUT_DTYPE).reshape(n)
+    # only the iterations some search ran cross PCIe (a timed search's bound is far above)
     live = max(1, int(out["iterations_run"].max())) if n else 1
+    return {"out": out, "rewards": d_rew[:, :live].cpu().numpy(), "hit_flags": d_flags[:, :live].cpu().numpy(),
+            "nodes": d_nodes}
+
+
+def _leaf_search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, iters, c, use_tt, tl_us, model, max_turns, bias_w):
+    """_search_on_device's bk_mcts_learned launch for search_packed's leaf agents.  Adds
+    bias_updates and children to the result: children[j] = the root's children of search j
+    as [move, visits, total, prior_bias] in expansion order."""
+    import torch
+
+    from .. import _native as N
+    from ..gpu import mcts_node_cap
+    n = len(ags)
+    dev = f"cuda:{gpu.device}"
+    cap_nodes = mcts_node_cap(iters)
+    d_prior = torch.zeros((n, cap_nodes), dtype=torch.float64, device=dev) if bias_w != 0.0 else None
+    d_bias = torch.zeros(n, dtype=torch.int32, device=dev)
+    r = _search_on_device(gpu, ags, functools.partial(gpu.mcts_learned_device, model=model, bias_updates=d_bias,
+                                                      max_turns=max_turns, bias_weight=bias_w, prior_bias=d_prior),
+                          rts, sts, pl, rh, zob, zidx, iters, c, use_tt, tl_us)
+    d_nodes = r.pop("nodes")
     # the roots' child blocks (and their prior biases) in one gather each
     root = d_nodes.view(n, cap_nodes, N.MCTS_NODE_DTYPE.itemsize)[:, 0, :].cpu().numpy().view(N.MCTS_NODE_DTYPE).reshape(n)
     where = np.concatenate([j * cap_nodes + int(root["child0"][j]) + np.arange(int(root["n_exp"][j]), dtype=np.int64)
@@ -141,50 +163,71 @@ def _leaf_search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, iters, c, use_
         children.append([[int(kids["move"][at + i]), int(kids["visits"][at + i]), float(kids["total"][at + i]),
                           float(pri[at + i])] for i in range(k)])
         at += k
-    return {"out": out, "rewards": d_rew[:, :live].cpu().numpy(), "hit_flags": d_flags[:, :live].cpu().numpy(),
-            "bias_updates": d_bias.cpu().numpy(), "children": children}
+    return dict(r, bias_updates=d_bias.cpu().numpy(), children=children)
 
 
-def _search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, mt, iters, max_roll, c, use_tt, tl_us, policy):
-    """One bk_mcts launch for search_packed with every buffer in HBM (BK_MEM_DEVICE).
-    The agents' TTs stay on the device between calls (TTPool rows, gathered into the
-    launch's [n, cap] block and scattered back); only the roots, streams and per-search
-    outputs cross PCIe.  mt (uint32[n, 625]) is advanced in place.  Returns dict(out,
-    rewards, hit_flags) as host arrays."""
+def _rollout_search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, mt, iters, max_roll, c, use_tt, tl_us, policy):
+    """_search_on_device's bk_mcts launch; the agents' streams mt (uint32[n, 625]) cross PCIe
+    too and are advanced in place."""
     import torch
-
-    from .. import _native as N
-    from ..gpu import TT_LOCK, mcts_log_table, mcts_node_cap
-    n = len(ags)
-    dev = f"cuda:{gpu.device}"
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    lts = gpu.__dict__.setdefault("_log_tables", {})
-    if iters not in lts:
-        lts[iters] = up(mcts_log_table(iters))
-    cap_nodes = mcts_node_cap(iters)
-    d_mt = up(mt.view(np.int32))
-    d_out = torch.zeros((n, N.MCTS_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-    d_rew = torch.empty((n, iters), dtype=torch.float64, device=dev)
-    d_flags = torch.empty((n, iters), dtype=torch.uint8, device=dev)
-    tk = tv = tc = rows = pool = None
-    # TT_LOCK from the rows' lease / gather to their scatter (synchronized by the count
-    # copy): another thread's search or pool growth cannot interleave (gpu.TT_LOCK)
-    with (TT_LOCK if use_tt else contextlib.nullcontext()):
-        if use_tt:
-            pool, rows, tk, tv, tc = _tt_gather(gpu, ags, iters, dev)
-        gpu.mcts_device(up(rts.view(np.uint8).reshape(n, 256)), up(sts.view(np.uint8).reshape(n, -1)), up(pl),
-                        up(rh.view(np.int64)), up(zob.view(np.int64)), up(zidx), d_mt, lts[iters],
-                        torch.empty((n, cap_nodes * N.MCTS_NODE_DTYPE.itemsize), dtype=torch.uint8, device=dev),
-                        d_out, iterations=iters, tt_keys=tk, tt_vals=tv, tt_count=tc, rewards=d_rew,
-                        hit_flags=d_flags, max_rollout_moves=max_roll, exploration=c, rollout_policy=policy,
-                        time_limit_us=tl_us)
-        if use_tt:
-            _tt_scatter(ags, pool, rows, tk, tv, tc)  # synchronizes this stream
+    d_mt = torch.from_numpy(np.ascontiguousarray(mt.view(np.int32))).to(f"cuda:{gpu.device}")
+    r = _search_on_device(gpu, ags, functools.partial(gpu.mcts_device, mt_state=d_mt, max_rollout_moves=max_roll,
+                                                      rollout_policy=policy),
+                          rts, sts, pl, rh, zob, zidx, iters, c, use_tt, tl_us)
     mt[:] = d_mt.cpu().numpy().view(np.uint32)
-    out = d_out.cpu().numpy().view(N.MCTS_OUT_DTYPE).reshape(n)
-    # only the iterations some search ran cross PCIe (a timed search's bound is far above)
-    live = max(1, int(out["iterations_run"].max())) if n else 1
-    return {"out": out, "rewards": d_rew[:, :live].cpu().numpy(), "hit_flags": d_flags[:, :live].cpu().numpy()}
+    return r
+
+
+def _pack_roots(ags, roots, sets, players, idx):
+    """The positions of one launch's searches `idx`, each hashed with its agent's Zobrist
+    table: (roots, sets, players, zobrist, zobrist_index, root_hash)."""
+    from .zobrist import flat_keys, hash_states
+    rts = np.ascontiguousarray(roots[idx])
+    sts = np.ascontiguousarray(sets[idx])
+    pl = np.array([players[i] for i in idx], np.uint8)
+    rts["current_player"] = pl
+    zob = np.stack([flat_keys(a.zobrist_hash) for a in ags])  # one table per search
+    return rts, sts, pl, zob, np.arange(len(ags), dtype=np.int32), hash_states(rts, zob)
+
+
+def _per_search(idx, ags, r):
+    """(i, agent, best move or None, iterations_run, tt_hits, rollouts, rewards) of each search
+    of a launch's result r, as Python values in one pass (structured-scalar access is slow);
+    rewards: the search's non-hit rewards in order."""
+    ro = r["out"]
+    # NaN marks a TT hit or an iteration past the search's end: rewards are finite
+    its = np.arange(r["rewards"].shape[1])[None, :]
+    live = (r["hit_flags"] == 0) & (its < ro["iterations_run"][:, None])
+    rew_rows = np.where(live, r["rewards"], np.nan).tolist()
+    best = [b if b >= 0 else None for b in ro["best_move"].tolist()]
+    return zip(idx, ags, best, ro["iterations_run"].tolist(), ro["tt_hits"].tolist(), ro["rollouts"].tolist(),
+               [[x for x in row if x == x] for row in rew_rows])
+
+
+def _record_search(a, iters, tl_us, use_tt, dt, n_it, hits, sims, rewards):
+    """One finished search into its agent's stats and TT counters, as select_action leaves
+    them: n_it iterations, of which `hits` TT hits and `sims` rollouts or leaf evaluations
+    (the TT's misses) that drew `rewards`."""
+    a.stats["iterations_run"] = n_it
+    if tl_us:
+        a.stats["iteration_bound"] = iters
+        a.stats["iteration_bound_reached"] = n_it >= iters
+        if a.stats["iteration_bound_reached"]:
+            warnings.warn(f"MCTSAgent: a {a.time_limit} s search stopped at its {iters}-iteration "
+                          "bound before the time ran out", RuntimeWarning, stacklevel=3)
+    a.stats["time_elapsed"] = dt
+    a.stats["transposition_hits"] += hits
+    a.stats["rollout_rewards"].extend(rewards)
+    if use_tt:
+        t = a.transposition_table
+        t.access_count += hits + sims
+        t.hit_count += hits
+        t.gpu_size = int(a._gpu_tt.count[0])
+        if t.gpu_size > 500000:  # mcts_agent.py:338-339
+            t.clear()
+            a._gpu_tt.release()
+            a._gpu_tt = None
+
 
 _MT_VIEWS_OK: Optional[bool] = None
 
@@ -246,6 +289,16 @@ SEARCH_TOTALS: Dict[str, Any] = {"launches": 0, "kernel_ms": 0.0, "sims": 0, "ro
 
 def reset_search_totals() -> None:
     SEARCH_TOTALS.update(launches=0, kernel_ms=0.0, sims=0, rollout_plies=0, by_kernel={})
+
+
+def add_search_launch(kernel: str, kernel_ms: float, sims: int, plies: int) -> None:
+    """One launch of `kernel` into SEARCH_TOTALS and into its "by_kernel" entry."""
+    for tot in (SEARCH_TOTALS, SEARCH_TOTALS["by_kernel"].setdefault(
+            kernel, {"launches": 0, "kernel_ms": 0.0, "sims": 0, "rollout_plies": 0})):
+        tot["launches"] += 1
+        tot["kernel_ms"] += kernel_ms
+        tot["sims"] += sims
+        tot["rollout_plies"] += plies
 
 # Timed searches (time_limit): iteration bound per second of limit, and overall.  One
 # search runs ~100-1,000 iterations/s on the GPU (a lane of a persistent wave), so the
@@ -458,7 +511,6 @@ class MCTSAgent:
         bk_mcts launch per parameter group.  Returns move ints (g * 400 + cell)."""
         from .. import _native as N
         from ..gpu import BlokusGPU
-        from .zobrist import flat_keys, hash_states
         assert len({id(a) for a in agents}) == len(agents), "one search per agent per launch"
         out: List[Optional[int]] = [None] * len(agents)
         groups = {}  # agents sharing (iterations, rollout cap, c, TT on/off, time limit) share a launch
@@ -496,16 +548,7 @@ class MCTSAgent:
             iters, max_roll, c, use_tt, tl_us, policy = key
             ags = [agents[i] for i in idx]
             gpu = BlokusGPU.shared(ags[0].device)
-            rts = np.ascontiguousarray(roots[idx])
-            sts = np.ascontiguousarray(sets[idx])
-            pl = np.array([players[i] for i in idx], np.uint8)
-            rts["current_player"] = pl
-            tabs, zidx = [], []
-            for a in ags:
-                tabs.append(flat_keys(a.zobrist_hash))
-                zidx.append(len(tabs) - 1)
-            zob = np.stack(tabs)
-            rh = hash_states(rts, zob)  # one table per search
+            rts, sts, pl, zob, zidx, rh = _pack_roots(ags, roots, sets, players, idx)
             views = [_mt_view(a.rollout_agent.rng) for a in ags]
             if all(v is not None for v in views):
                 mt = np.stack(views)  # a copy: the kernel advances it, written back below
@@ -517,57 +560,26 @@ class MCTSAgent:
                     mt[j, :624] = st[1]
                     mt[j, 624] = st[2]
             t0 = time.time()
-            r = _search_on_device(gpu, ags, rts, sts, pl, rh, zob, np.array(zidx, np.int32), mt, iters, max_roll, c,
-                                  use_tt, tl_us, policy)
+            r = _rollout_search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, mt, iters, max_roll, c, use_tt, tl_us,
+                                          policy)
             dt = time.time() - t0
-            kms, ksims = gpu.last_kernel_ms(), int(r["out"]["iterations_run"].sum())
-            kplies = int(r["out"]["rollout_plies"].astype(np.int64).sum())
-            for tot in (SEARCH_TOTALS, SEARCH_TOTALS["by_kernel"].setdefault(
-                    gpu.last_kernel(), {"launches": 0, "kernel_ms": 0.0, "sims": 0, "rollout_plies": 0})):
-                tot["launches"] += 1
-                tot["kernel_ms"] += kms
-                tot["sims"] += ksims
-                tot["rollout_plies"] += kplies
-            # the non-hit rewards of every search as Python lists in one pass (NaN marks a
-            # TT hit or an iteration past the search's end: rewards are finite)
-            its = np.arange(r["rewards"].shape[1])[None, :]
-            live = (r["hit_flags"] == 0) & (its < r["out"]["iterations_run"][:, None])
-            rew_rows = np.where(live, r["rewards"], np.nan).tolist()
-            ro = r["out"]  # per-search fields as Python ints (structured-scalar access is slow)
-            f_it, f_hits, f_roll = ro["iterations_run"].tolist(), ro["tt_hits"].tolist(), ro["rollouts"].tolist()
-            f_status, f_best = ro["status"].tolist(), ro["best_move"].tolist()
-            for j, (i, a) in enumerate(zip(idx, ags)):
+            ro = r["out"]
+            add_search_launch(gpu.last_kernel(), gpu.last_kernel_ms(), int(ro["iterations_run"].sum()),
+                              int(ro["rollout_plies"].astype(np.int64).sum()))
+            f_status = ro["status"].tolist()
+            for j, (i, a, best, *done) in enumerate(_per_search(idx, ags, r)):
                 if rng_states is None:
                     views[j][:] = mt[j]
                 else:
                     st = rng_states[j]
                     a.rollout_agent.rng.set_state((st[0], mt[j, :624].copy(), int(mt[j, 624]), st[3], st[4]))
-                n_it = f_it[j]
-                a.stats["iterations_run"] = n_it
                 # HeuristicAgent rollouts: a draw within 2^-40 of a probability boundary
                 # (BK_MCTS_EUNCERT; the kernel flags the search, it does not count draws)
                 unc = bool(f_status[j] & N.MCTS_EUNCERT)
                 a.stats["last_search_uncertified"] = unc
                 a.stats["uncertified_searches"] = a.stats.get("uncertified_searches", 0) + int(unc)
-                if tl_us:
-                    a.stats["iteration_bound"] = iters
-                    a.stats["iteration_bound_reached"] = n_it >= iters
-                    if a.stats["iteration_bound_reached"]:
-                        warnings.warn(f"MCTSAgent: a {a.time_limit} s search stopped at its {iters}-iteration "
-                                      "bound before the time ran out", RuntimeWarning, stacklevel=2)
-                a.stats["time_elapsed"] = dt
-                a.stats["transposition_hits"] += f_hits[j]
-                a.stats["rollout_rewards"].extend([x for x in rew_rows[j] if x == x])
-                if use_tt:
-                    t = a.transposition_table
-                    t.access_count += f_hits[j] + f_roll[j]
-                    t.hit_count += f_hits[j]
-                    t.gpu_size = int(a._gpu_tt.count[0])
-                    if t.gpu_size > 500000:  # mcts_agent.py:338-339
-                        t.clear()
-                        a._gpu_tt.release()
-                        a._gpu_tt = None
-                out[i] = f_best[j] if f_best[j] >= 0 else None
+                _record_search(a, iters, tl_us, use_tt, dt, *done)
+                out[i] = best
         return out
 
     @staticmethod
@@ -575,56 +587,22 @@ class MCTSAgent:
         """search_packed's launch for one group of "leaf" agents; stats as the exact backend
         leaves them (leaf_eval_calls, progressive_bias_updates, the non-hit rewards)."""
         from ..gpu import BlokusGPU
-        from .zobrist import flat_keys, hash_states
         _, iters, c, use_tt, tl_us, _, max_turns, bias_w = key
         ags = [agents[i] for i in idx]
         gpu = BlokusGPU.shared(ags[0].device)
-        rts = np.ascontiguousarray(roots[idx])
-        sts = np.ascontiguousarray(sets[idx])
-        pl = np.array([players[i] for i in idx], np.uint8)
-        rts["current_player"] = pl
-        zob = np.stack([flat_keys(a.zobrist_hash) for a in ags])
-        rh = hash_states(rts, zob)  # one table per search
+        rts, sts, pl, zob, zidx, rh = _pack_roots(ags, roots, sets, players, idx)
         t0 = time.time()
-        r = _leaf_search_on_device(gpu, ags, rts, sts, pl, rh, zob, np.arange(len(ags), dtype=np.int32), iters, c,
-                                   use_tt, tl_us, ags[0].learned_evaluator.model, max_turns, bias_w)
+        r = _leaf_search_on_device(gpu, ags, rts, sts, pl, rh, zob, zidx, iters, c, use_tt, tl_us,
+                                   ags[0].learned_evaluator.model, max_turns, bias_w)
         dt = time.time() - t0
-        kms, ro = gpu.last_kernel_ms(), r["out"]
-        for tot in (SEARCH_TOTALS, SEARCH_TOTALS["by_kernel"].setdefault(
-                gpu.last_kernel(), {"launches": 0, "kernel_ms": 0.0, "sims": 0, "rollout_plies": 0})):
-            tot["launches"] += 1
-            tot["kernel_ms"] += kms
-            tot["sims"] += int(ro["iterations_run"].sum())
-        its = np.arange(r["rewards"].shape[1])[None, :]
-        live = (r["hit_flags"] == 0) & (its < ro["iterations_run"][:, None])
-        rew_rows = np.where(live, r["rewards"], np.nan).tolist()
-        for j, (i, a) in enumerate(zip(idx, ags)):
-            n_it, hits, evals = int(ro["iterations_run"][j]), int(ro["tt_hits"][j]), int(ro["rollouts"][j])
-            a.stats["iterations_run"] = n_it
+        add_search_launch(gpu.last_kernel(), gpu.last_kernel_ms(), int(r["out"]["iterations_run"].sum()), 0)
+        for j, (i, a, best, n_it, hits, evals, rewards) in enumerate(_per_search(idx, ags, r)):
             a.stats["last_search_uncertified"] = False
-            if tl_us:
-                a.stats["iteration_bound"] = iters
-                a.stats["iteration_bound_reached"] = n_it >= iters
-                if a.stats["iteration_bound_reached"]:
-                    warnings.warn(f"MCTSAgent: a {a.time_limit} s search stopped at its {iters}-iteration "
-                                  "bound before the time ran out", RuntimeWarning, stacklevel=2)
-            a.stats["time_elapsed"] = dt
-            a.stats["transposition_hits"] += hits
             a.stats["leaf_eval_calls"] += evals
             a.stats["progressive_bias_updates"] += int(r["bias_updates"][j])
-            a.stats["rollout_rewards"].extend([x for x in rew_rows[j] if x == x])
             a.last_root_children = r["children"][j]
-            if use_tt:
-                t = a.transposition_table
-                t.access_count += hits + evals
-                t.hit_count += hits
-                t.gpu_size = int(a._gpu_tt.count[0])
-                if t.gpu_size > 500000:  # mcts_agent.py:338-339
-                    t.clear()
-                    a._gpu_tt.release()
-                    a._gpu_tt = None
-            best = int(ro["best_move"][j])
-            out[i] = best if best >= 0 else None
+            _record_search(a, iters, tl_us, use_tt, dt, n_it, hits, evals, rewards)
+            out[i] = best
 
     def _get_move_positions(self, move: Move) -> List[Position]:
         return _positions(move)

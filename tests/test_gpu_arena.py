@@ -262,3 +262,79 @@ def test_arena_step_skip_leaves_games_untouched():
     for got, ref in zip((st, fs, rs, out), full[:4]):
         assert np.array_equal(got[kept], ref[kept])
     assert not np.array_equal(st[kept], b0[0].cpu().numpy()[kept])  # they did play
+
+
+def test_arena_entry_points_reject_bad_arguments():
+    """What bk_arena_advance, bk_arena_step and bk_arena_step_snap reject, each naming itself:
+    another semantics, order or rng, seats sharing a stream, a missing buffer, quick_masks
+    without stop_out, a misaligned rng_state in device memory, a forced move out of range in
+    host memory, bk_arena_step_snap's plan and host-memory cases.  n == 0 is BK_OK.  Every row
+    is BK_EINVAL before anything is launched; the buffers stay as they were."""
+    import ctypes as C
+
+    import torch
+
+    from reinforcementlearning_blokus_amd import _native as N
+    from reinforcementlearning_blokus_amd.gpu import BlokusGPU, empty_state
+    gpu = BlokusGPU(0)
+    h = gpu.handle
+    h.set_stream(None)
+    n = 2
+    host = dict(states=np.repeat(empty_state(), n), sets=N.fset_new(n), masks=np.full(n, 0x01, np.uint8),
+                quick=np.zeros(n, np.uint8), forced=np.full(n, -1, np.int32), out=np.zeros(n, N.RESULT_DTYPE),
+                rng=np.stack([N.mt_cursors([7000 + 4 * i + p for p in range(4)]).reshape(-1) for i in range(n)]),
+                stop=np.zeros(n, N.STOP_DTYPE))
+    dev = {k: torch.from_numpy(v.view(np.uint8).reshape(n, -1)).to("cuda:0") for k, v in host.items()}
+    slots = {k: torch.zeros((n, 1, w), dtype=torch.uint8, device="cuda:0") for k, w in
+             (("states", 256), ("sets", N.FSET_DTYPE.itemsize), ("turn", 4))}
+    before = {k: v.copy() for k, v in host.items()}
+
+    def plan(mask=(2, 0, 0, 0), **null):
+        return N.BkSnapPlan((C.c_uint32 * 4)(*mask), *(0 if k in null else slots[k].data_ptr()
+                                                        for k in ("states", "sets", "turn")))
+
+    def run(name, mem=N.MEM_HOST, n=n, cfg=(N.SEM_ARENA, N.ORDER_FRONTIER, N.RNG_NUMPY_MT, 0), rng_offset=0,
+            plan=plan(), **null):
+        src = host if mem == N.MEM_HOST else dev
+        p = {k: 0 if k in null else (v.ctypes.data if mem == N.MEM_HOST else v.data_ptr()) for k, v in src.items()}
+        rcfg = N.BkRolloutCfg(cfg[0], cfg[1], cfg[2], 12, 0, cfg[3], 0)
+        if name == "bk_arena_advance":
+            return h.arena_advance(p["states"], p["sets"], n, rcfg, p["masks"], p["rng"] + rng_offset, p["out"], mem)
+        args = (p["states"], p["sets"], n, rcfg, p["masks"], p["quick"], p["forced"], p["rng"] + rng_offset,
+                p["out"], p["stop"])
+        return h.arena_step(*args, mem) if name == "bk_arena_step" else h.arena_step_snap(*args, plan, mem)
+
+    def rejected(name, text, **kw):
+        with pytest.raises(RuntimeError) as err:
+            run(name, **kw)
+        assert f"{name} failed ({N.EINVAL}): {name}: {text}" in str(err.value), (kw, str(err.value))
+
+    good = (N.SEM_ARENA, N.ORDER_FRONTIER, N.RNG_NUMPY_MT, 0)
+    for name in ("bk_arena_advance", "bk_arena_step", "bk_arena_step_snap"):
+        mem = N.MEM_DEVICE if name == "bk_arena_step_snap" else N.MEM_HOST
+        for field, value in ((0, N.SEM_ROLLOUT), (1, N.ORDER_NAIVE), (2, N.RNG_PHILOX), (3, 1)):
+            cfg = tuple(value if k == field else g for k, g in enumerate(good))
+            rejected(name, "needs ARENA, FRONTIER order, NUMPY_MT per-seat streams", mem=mem, cfg=cfg)
+        for k in ("states", "sets", "masks", "rng", "out"):
+            rejected(name, "invalid arguments", mem=mem, **{k: True})
+        rejected(name, "invalid arguments", mem=mem, n=-1)
+        rejected(name, "rng_state must be 16-byte aligned", mem=N.MEM_DEVICE, rng_offset=8)
+        run(name, mem=mem, n=0)
+    for name in ("bk_arena_step", "bk_arena_step_snap"):
+        rejected(name, "quick_masks goes with stop_out", mem=N.MEM_DEVICE, stop=True)
+    for move in (N.FORCE_SKIP - 1, 91 * 400):
+        host["forced"][1] = move
+        rejected("bk_arena_step", "forced move out of range")
+        host["forced"][1] = -1
+    snap = dict(name="bk_arena_step_snap", mem=N.MEM_DEVICE)
+    rejected(text="BK_MEM_DEVICE only", name="bk_arena_step_snap", mem=N.MEM_HOST)
+    for k in ("states", "sets", "turn"):
+        rejected(text="a plan with states, sets and turn", plan=plan(**{k: True}), **snap)
+    odd = N.BkSnapPlan((C.c_uint32 * 4)(2, 0, 0, 0), slots["states"].data_ptr(), slots["sets"].data_ptr() + 8,
+                       slots["turn"].data_ptr())
+    rejected(text="the plan's sets must be 16-byte", plan=odd, **snap)
+    rejected(text="the ply mask is empty", plan=plan(mask=(0, 0, 0, 0)), **snap)
+    rejected(text="ply 0 is not captured here", plan=plan(mask=(3, 0, 0, 0)), **snap)
+    gpu.synchronize()
+    for k, v in host.items():
+        assert v.tobytes() == before[k].tobytes() == dev[k].cpu().numpy().tobytes(), k
