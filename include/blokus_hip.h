@@ -742,6 +742,77 @@ int bk_winprob_eval(bk_handle h, const bk_state* states, const bk_fset* sets, in
                     double* prob, double* pair_logit, uint8_t* status, int mem);
 
 /*
+ * bk_winprob_eval_gbt -- the learned evaluator of mcts/learned_evaluator.py for a
+ * "pairwise_gbt_phase" artifact: one gradient-boosted tree ensemble (sklearn
+ * GradientBoostingClassifier, binary, log_loss) per game phase, n boards and all four players
+ * of each in one launch (k_winprob_gbt; added within ABI 7: new symbols only).  The block
+ * builds the board's four snapshot rows as bk_winprob_eval does, then scores player p against
+ * each opponent q, q ascending:
+ *     x_k = f[p][k] - f[q][k];  z_k = (x_k - mean[k]) / scale[k];  xf_k = (float)z_k
+ *     occupancy = (f[p][occ] + f[q][occ]) / 2.0, occ = phase_board_occupancy (column 29)
+ *     phase = 0 (early) if occupancy < 0.33, 1 (mid) if < 0.66, else 2 (late)
+ *     t = init;  for each tree of the phase's ensemble, in order:
+ *         walk from the root: at an inner node go to `left` if (double)xf[feature] <= tv,
+ *         else to `left + 1`;  t = t + learning_rate * (the leaf's tv)
+ *     s = 1 / (1 + exp(-t));  prob[4 i + p] = ((s_q0 + s_q1) + s_q2) / 3.0
+ * every step one correctly rounded operation (no FMA), so pair_raw[(4 i + p) * 3 + j] equals
+ * sklearn's decision_function of that pair bit for bit; exp and the status word are
+ * bk_winprob_eval's.  sklearn's missing-value branch is not modelled (a row is finite whenever
+ * the status is 0).
+ *
+ * The model is too large for the kernel arguments: bk_gbt_model_load copies it to device
+ * memory owned by the handle once and returns an id for later evaluations.
+ */
+typedef struct bk_gbt_node {     /* POD, 16 bytes */
+    double  tv;                  /* inner node: the threshold; leaf: the leaf's value              */
+    int32_t left;                /* inner node: its children are left and left + 1, both greater
+                                    than the node's own index; leaf: -1                            */
+    int32_t feature;             /* 0 .. BK_SNAPSHOT_COLUMNS - 1 (a leaf: 0)                       */
+} bk_gbt_node;
+typedef struct bk_gbt_phase {    /* POD, 24 bytes: one phase's ensemble */
+    double  init;                /* the raw prior added first (0 for init="zero")                  */
+    double  learning_rate;
+    int32_t first_tree, n_trees; /* its stages are tree_root[first_tree .. first_tree + n_trees)   */
+} bk_gbt_phase;
+typedef struct bk_gbt_model {            /* POD, 616 bytes; columns in BK_SNAPSHOT_COLUMNS order  */
+    double mean[BK_SNAPSHOT_COLUMNS];    /* StandardScaler mean_  (0 where absent)                */
+    double scale[BK_SNAPSHOT_COLUMNS];   /* StandardScaler scale_ (1 where absent)                */
+    bk_gbt_phase phase[3];               /* early, mid, late; phases may share one range          */
+} bk_gbt_model;
+#define BK_GBT_MAX_TREES 4096     /* tree roots of one model (all phases together)                 */
+#define BK_GBT_MAX_NODES 1048576  /* nodes of one model: 16 MiB of device memory at the most       */
+#define BK_GBT_SLOTS 4            /* models resident on one handle at a time                       */
+/* sizeof the structs as the library was compiled (binding checks; no GPU call). */
+int bk_gbt_node_size(void);
+int bk_gbt_model_size(void);
+/* Pure host check, no handle and no GPU: BK_OK if the model can be handed to the kernel, else
+   BK_EINVAL with the reason in reason[0 .. reason_len) (may be NULL).  It holds unless:
+   1 <= n_trees <= BK_GBT_MAX_TREES and 1 <= n_nodes <= BK_GBT_MAX_NODES; every mean, scale,
+   init, learning_rate and tv is finite and no scale is 0; every phase has n_trees >= 1 and its
+   range lies inside tree_root; every root is a node index; every feature is in 0..33; every
+   left is -1 or has left > the node's own index and left + 1 < n_nodes.  The child-index rule
+   is what makes every walk end: a model that fails the check never reaches the kernel. */
+int bk_gbt_model_check(const bk_gbt_model* model, const int32_t* tree_root, int32_t n_trees,
+                       const bk_gbt_node* nodes, int32_t n_nodes, char* reason, size_t reason_len);
+/* Runs the check (BK_EINVAL, the reason in bk_last_error), then copies the model to device
+   memory owned by h and sets *model_id (> 0).  All arguments are host pointers.  BK_EOVERFLOW
+   when all BK_GBT_SLOTS slots are taken.  bk_gbt_model_free waits for the handle's stream to
+   be idle, then releases the slot; the id is refused from then on (ids are never reused). */
+int bk_gbt_model_load(bk_handle h, const bk_gbt_model* model, const int32_t* tree_root, int32_t n_trees,
+                      const bk_gbt_node* nodes, int32_t n_nodes, int32_t* model_id);
+int bk_gbt_model_free(bk_handle h, int32_t model_id);
+/* As bk_winprob_eval argument for argument, with model_id in the model's place: turn_index may
+   be NULL (each board's move_count); prob (n x 4) and status (n) are required, pair_raw
+   (n x 4 x 3, the t values) may be NULL; mem as bk_snapshot_features (device pointers: sets
+   16-byte, states, prob and pair_raw 8-byte, turn_index 4-byte aligned).  BK_EINVAL, before any
+   GPU work, for null states, sets, prob or status, n < 0, max_turns < 0, and a model_id that
+   was never returned or has been freed; n == 0 is BK_OK without a launch; timed for
+   bk_last_kernel_ms ("k_winprob_gbt"). */
+int bk_winprob_eval_gbt(bk_handle h, const bk_state* states, const bk_fset* sets, int32_t n,
+                        const int32_t* turn_index, int32_t max_turns, int32_t model_id,
+                        double* prob, double* pair_raw, uint8_t* status, int mem);
+
+/*
  * bk_mcts_learned -- bk_mcts searches whose simulations are learned leaf evaluations
  * (mcts/mcts_agent.py:408-468 with leaf_evaluation_enabled, optionally
  * progressive_bias_enabled), whole in one launch (k_mcts_coop_l, one wave per search; added

@@ -42,6 +42,8 @@ EXPORTS = (
     "bk_step_metrics", "bk_step_rec_size",
     "bk_arena_step_snap", "bk_snap_plan_size",
     "bk_mcts_learned",
+    "bk_gbt_node_size", "bk_gbt_model_size", "bk_gbt_model_check", "bk_gbt_model_load", "bk_gbt_model_free",
+    "bk_winprob_eval_gbt",
 )
 # bk_debug_mcts_failure record (include/blokus_hip.h BK_DIAG_*)
 DIAG_WORDS = 64
@@ -193,6 +195,26 @@ class BkWinprobModel(C.Structure):
 assert C.sizeof(BkWinprobModel) == 8 * (3 * SNAPSHOT_COLUMNS + 1)
 
 
+class BkGbtPhase(C.Structure):
+    """bk_gbt_phase: one phase's ensemble, a range of the model's tree roots."""
+    _fields_ = [("init", C.c_double), ("learning_rate", C.c_double), ("first_tree", C.c_int32),
+                ("n_trees", C.c_int32)]
+
+
+class BkGbtModel(C.Structure):
+    """bk_gbt_model: the scaler and the three phases (early, mid, late) of a pairwise_gbt_phase model."""
+    _fields_ = [("mean", C.c_double * SNAPSHOT_COLUMNS), ("scale", C.c_double * SNAPSHOT_COLUMNS),
+                ("phase", BkGbtPhase * 3)]
+
+
+# bk_gbt_node: tv the threshold (inner node) or the value (leaf, left = -1); children left, left + 1
+GBT_NODE_DTYPE = np.dtype([("tv", "<f8"), ("left", "<i4"), ("feature", "<i4")])
+GBT_MAX_TREES, GBT_MAX_NODES, GBT_SLOTS = 4096, 1 << 20, 4  # BK_GBT_MAX_TREES, BK_GBT_MAX_NODES, BK_GBT_SLOTS
+GBT_PHASES = ("early", "mid", "late")
+assert C.sizeof(BkGbtPhase) == 24 and C.sizeof(BkGbtModel) == 16 * SNAPSHOT_COLUMNS + 72
+assert GBT_NODE_DTYPE.itemsize == 16
+
+
 STEP_ST_TABLE, STEP_ST_STATE, STEP_ST_MOVE = 1, 2, 4  # bk_step_rec.status bits
 # bk_step: one logged move (mover 0..3, the reference's Move fields)
 STEP_DTYPE = np.dtype([("mover", "u1"), ("piece_id", "u1"), ("orientation", "u1"), ("anchor_row", "u1"),
@@ -331,6 +353,12 @@ def load():
             "bk_mcts_learned": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, P(BkMctsCfg), vp, C.c_int32, vp, vp, vp, vp,
                                           vp, C.c_int32, P(BkWinprobModel), C.c_int32, C.c_double, vp, vp, vp, vp,
                                           vp, vp, C.c_int]),
+            "bk_gbt_node_size": (C.c_int, []),
+            "bk_gbt_model_size": (C.c_int, []),
+            "bk_gbt_model_check": (C.c_int, [P(BkGbtModel), vp, C.c_int32, vp, C.c_int32, C.c_char_p, C.c_size_t]),
+            "bk_gbt_model_load": (C.c_int, [vp, P(BkGbtModel), vp, C.c_int32, vp, C.c_int32, P(C.c_int32)]),
+            "bk_gbt_model_free": (C.c_int, [vp, C.c_int32]),
+            "bk_winprob_eval_gbt": (C.c_int, [vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int]),
         }
         for name, (res, args) in sigs.items():
             f = getattr(L, name)
@@ -422,6 +450,16 @@ def pow_half_fix(log_table: np.ndarray, rows: int | None = None, cached_only: bo
     if rows >= have:
         c.update(lt=lt[:rows].copy(), off=off, ent=ent)
     return off, ent
+
+
+def gbt_model_check(model: BkGbtModel, tree_root, nodes):
+    """bk_gbt_model_check (host only, no GPU): None if the kernel may be handed the model, else
+    the reason.  tree_root: int32 node indices; nodes: GBT_NODE_DTYPE records."""
+    roots = np.ascontiguousarray(tree_root, dtype=np.int32)
+    nd = np.ascontiguousarray(nodes, dtype=GBT_NODE_DTYPE)
+    buf = C.create_string_buffer(256)
+    rc = load().bk_gbt_model_check(C.byref(model), roots.ctypes.data, len(roots), nd.ctypes.data, len(nd), buf, 256)
+    return None if rc == OK else buf.value.decode(errors="replace")
 
 
 def mt_cursors(seeds) -> np.ndarray:
@@ -718,6 +756,31 @@ class Handle:
                                          C.c_void_p(prob_ptr or 0), C.c_void_p(logit_ptr or 0),
                                          C.c_void_p(status_ptr or 0), mem)
         self.check(rc, "bk_winprob_eval")
+
+    def gbt_model_load(self, model: BkGbtModel, tree_root: np.ndarray, nodes: np.ndarray) -> int:
+        """bk_gbt_model_load: the id of the model's copy in device memory (one of GBT_SLOTS)."""
+        roots = np.ascontiguousarray(tree_root, dtype=np.int32)
+        nd = np.ascontiguousarray(nodes, dtype=GBT_NODE_DTYPE)
+        model_id = C.c_int32()
+        with self._lock:
+            rc = self._L.bk_gbt_model_load(self._h, C.byref(model), roots.ctypes.data, len(roots), nd.ctypes.data,
+                                           len(nd), C.byref(model_id))
+        self.check(rc, "bk_gbt_model_load")
+        return int(model_id.value)
+
+    def gbt_model_free(self, model_id: int):
+        with self._lock:
+            rc = self._L.bk_gbt_model_free(self._h, int(model_id))
+        self.check(rc, "bk_gbt_model_free")
+
+    def winprob_eval_gbt(self, states_ptr, sets_ptr, n, turn_ptr, max_turns, model_id, prob_ptr, raw_ptr, status_ptr,
+                         mem):
+        with self._lock:
+            rc = self._L.bk_winprob_eval_gbt(self._h, C.c_void_p(states_ptr or 0), C.c_void_p(sets_ptr or 0), n,
+                                             C.c_void_p(turn_ptr or 0), int(max_turns), int(model_id),
+                                             C.c_void_p(prob_ptr or 0), C.c_void_p(raw_ptr or 0),
+                                             C.c_void_p(status_ptr or 0), mem)
+        self.check(rc, "bk_winprob_eval_gbt")
 
     def step_metrics(self, before_ptr, sets_before_ptr, after_ptr, sets_after_ptr, steps_ptr, n, out_ptr, mem):
         with self._lock:

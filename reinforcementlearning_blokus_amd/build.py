@@ -45,7 +45,7 @@ def built_hash():
 # then one unit per kernel family, compiled in parallel and linked into one .so
 UNITS = {"host": 1, "movegen": 2, "rollout": 3, "rollout_fr": 4, "rollout_frh": 5, "fastmcts": 6,
          "mcts": 7, "mcts_pair": 8, "mcts_h": 9, "coop": 10, "coop_h": 11, "telemetry": 12,
-         "snapshot": 13, "steplog": 14, "rollout_frhs": 15, "coop_l": 16}
+         "snapshot": 13, "steplog": 14, "rollout_frhs": 15, "coop_l": 16, "gbt": 17}
 
 
 # per-unit code-generation flags (measured per kernel).  Machine LICM hoists

@@ -9,6 +9,7 @@
 //   engine/telemetry.py:17-198        collect_all_player_metrics (bk_telemetry)
 //   analytics/winprob/features.py:106-192 snapshot feature rows (bk_snapshot_features)
 //   mcts/learned_evaluator.py:95-144  pairwise_logreg win probabilities (bk_winprob_eval)
+//   mcts/learned_evaluator.py:111-124 pairwise_gbt_phase win probabilities (bk_winprob_eval_gbt)
 //   analytics/logging/logger.py:49-148 + analytics/metrics/* step-log integers (bk_step_metrics)
 //
 // Design (DESIGN.md has the full story):
@@ -73,6 +74,7 @@
 #define BK_U_STEPLOG 14
 #define BK_U_ROLLOUT_FRHS 15
 #define BK_U_COOP_L 16
+#define BK_U_GBT 17
 #ifndef BK_TU
 #define BK_TU 0
 #endif
@@ -6247,7 +6249,7 @@ struct WinprobArgs {
 static_assert(sizeof(bk_snapshot_rec) == 80 && sizeof(bk_snapshot_rec) % 8 == 0, "the record is copied out as dwords");
 static_assert(BK_SNAPSHOT_COLUMNS <= WAVE, "one lane per column");
 
-#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L)
+#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L) || BK_DEF(BK_U_GBT)
 // O_i (distinct orientations), S_i (cells) and the pieces of each size, from the orientation table
 struct SnapTab {
     uint8_t orients[BK_PIECES], size[BK_PIECES];
@@ -6393,7 +6395,7 @@ __device__ __forceinline__ void snap_row_fill(double* f, int lane, const SnapSca
 }
 #endif  // the snapshot routines
 
-#if BK_DEF(BK_U_SNAPSHOT)
+#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_GBT)
 // The four rows of one board (the block's), left in s_feat.  EVAL = false is k_snapshot: the
 // records and rows also go to global memory and a call without a.feat stops after the records.
 // EVAL = true is k_winprob: nothing is written to global memory, every wave builds its row
@@ -6542,7 +6544,9 @@ __device__ __forceinline__ uint32_t snap_rows(const SnapArgs& a, double (&s_feat
         a.feat[((size_t)board * 4 + (size_t)p) * BK_SNAPSHOT_COLUMNS + (size_t)lane] = f[lane];
     return status;
 }
+#endif  // snap_rows
 
+#if BK_DEF(BK_U_SNAPSHOT)
 __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
     __shared__ __attribute__((aligned(8))) double s_feat[SNAP_WAVES][BK_SNAPSHOT_COLUMNS];
     snap_rows<false>(a, s_feat);
@@ -6559,8 +6563,10 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
 // 172 on the edge boards 2 ulp from CPython's.  It overflows to +inf (s = 0) and underflows
 // to 0 (s = 1) for very large |t|.
 #endif  // BK_DEF(BK_U_SNAPSHOT)
-#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L)
+#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L) || BK_DEF(BK_U_GBT)
 #include "exp_cr.h"
+#endif
+#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L)
 // The chain's two steps for player p, shared with k_mcts_coop_l: lane k's three terms into
 // u[3][columns] (LDS), then -- after the wave's sync -- lane j < 3 sums opponent j's terms
 // (t, the pair logit) and returns the sigmoid.
@@ -6611,6 +6617,127 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_winprob(WinprobArgs a) {
 #else
 __global__ void k_snapshot(SnapArgs a);
 __global__ void k_winprob(WinprobArgs a);
+#endif
+
+// ------------------------------------------------------------------------------------
+// k_winprob_gbt: the learned evaluator for a pairwise_gbt_phase model (bk_winprob_eval_gbt;
+// mcts/learned_evaluator.py:111-124 with sklearn GradientBoostingClassifier ensembles).
+// k_winprob's mapping: one block of four waves per board, wave p for player p, the rows
+// from snap_rows<true> in LDS.  After the block barrier lane k < 34 forms
+// xf_k = (float)(((f[p][k] - f[q][k]) - mean[k]) / scale[k]) for the three opponents q and
+// leaves them in LDS (sklearn casts the row to float32 before it walks a tree); the phase of
+// each pair comes from the rows' occupancy column.  The trees are walked 64 stages at a time:
+// lane l walks stage 64 c + l for the three opponents at once -- per step one 16-byte node
+// load from global memory (the model lives in device memory, bk_gbt_model_load), one feature
+// read from LDS, one compare in double -- and leaves the three products lr * leaf in LDS; lane
+// j < 3 then continues opponent j's sum over the chunk in stage order, t = t + lr * v, one
+// rounding per operation (sklearn's order: the sum is bit for bit decision_function).  The
+// product goes through LDS as k_winprob's terms do: taken beside the add, the compiler fuses
+// the two into one v_fmac_f64 (the rounding intrinsics are inline functions of a header that
+// is compiled with contraction on), which rounds once and is not sklearn's value.  Every walk
+// ends and stays in bounds because bk_gbt_model_check admitted the model: a child's index is
+// greater than its parent's and below n_nodes, a feature below 34, a root below n_nodes.
+// The tail is k_winprob's: s = 1 / (1 + exp(-t)) with bk_exp_cr, the mean of three.
+// ------------------------------------------------------------------------------------
+struct __attribute__((aligned(16))) GbtNode {  // bk_gbt_node as the device reads it: one 16-byte load
+    double tv;
+    int32_t left, feature;
+};
+static_assert(sizeof(GbtNode) == sizeof(bk_gbt_node) && sizeof(bk_gbt_node) == 16, "one node, one dwordx4");
+static_assert(sizeof(bk_gbt_phase) == 24 && sizeof(bk_gbt_model) == 16 * BK_SNAPSHOT_COLUMNS + 72, "bk_gbt_model layout");
+#define GBT_OCC_COLUMN 29  // phase_board_occupancy
+struct GbtArgs {
+    SnapArgs s;                // rec and feat unused; turn_index may be null (each board's move_count)
+    const bk_gbt_model* m;     // device memory (the handle's slot)
+    const int32_t* roots;      // tree roots, the phases' ranges index it
+    const GbtNode* nodes;      // 16-byte aligned
+    double* prob;              // n x 4
+    double* pair_raw;          // n x 4 x 3 or null
+    uint8_t* status;           // n
+};
+
+#if BK_DEF(BK_U_GBT)
+__global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_winprob_gbt(GbtArgs a) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(8))) double s_feat[SNAP_WAVES][BK_SNAPSHOT_COLUMNS];
+    __shared__ float s_x[SNAP_WAVES][3][BK_SNAPSHOT_COLUMNS];
+    __shared__ __attribute__((aligned(8))) double s_v[SNAP_WAVES][3][WAVE];  // a chunk's lr * leaf value
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int p = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const size_t board = blockIdx.x;  // the grid is exactly n blocks
+    const uint32_t status = snap_rows<true>(a.s, s_feat);
+    __syncthreads();  // the four rows are complete
+    if (lane < BK_SNAPSHOT_COLUMNS) {
+        const double fp = s_feat[p][lane], mean = a.m->mean[lane], scale = a.m->scale[lane];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int q = j + (j >= p ? 1 : 0);
+            const double x = __dsub_rn(fp, s_feat[q][lane]);
+            s_x[p][j][lane] = __double2float_rn(__ddiv_rn(__dsub_rn(x, mean), scale));
+        }
+    }
+    // each pair's ensemble (wave-uniform): the phase of the pair's mean occupancy
+    int first[3], cnt[3], nmax = 0;
+    double lr[3];
+    double t = 0.0;  // lane j < 3: opponent j's running sum
+    int mine = 0;    // lane j < 3: opponent j's stage count
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int q = j + (j >= p ? 1 : 0);
+        const double occ = __ddiv_rn(__dadd_rn(s_feat[p][GBT_OCC_COLUMN], s_feat[q][GBT_OCC_COLUMN]), 2.0);
+        const int ph = __builtin_amdgcn_readfirstlane(occ < 0.33 ? 0 : (occ < 0.66 ? 1 : 2));
+        const bk_gbt_phase& e = a.m->phase[ph];
+        first[j] = e.first_tree;
+        cnt[j] = e.n_trees;
+        nmax = cnt[j] > nmax ? cnt[j] : nmax;
+        lr[j] = e.learning_rate;
+        if (lane == j) { t = e.init; mine = e.n_trees; }
+    }
+    tel_wave_sync();  // the wave's xf are complete
+    for (int c0 = 0; c0 < nmax; c0 += WAVE) {  // (uniform)
+        const int stage = c0 + lane;
+        int node[3];
+        double v[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) node[j] = stage < cnt[j] ? a.roots[first[j] + stage] : -1;
+        while (node[0] >= 0 || node[1] >= 0 || node[2] >= 0) {
+            GbtNode nd[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) nd[j] = a.nodes[node[j] >= 0 ? node[j] : 0];  // three loads in flight
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                if (node[j] < 0) continue;
+                if (nd[j].left < 0) {
+                    v[j] = nd[j].tv;
+                    node[j] = -1;
+                } else {
+                    node[j] = nd[j].left + ((double)s_x[p][j][nd[j].feature] <= nd[j].tv ? 0 : 1);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if (stage < cnt[j]) s_v[p][j][lane] = __dmul_rn(lr[j], v[j]);
+        tel_wave_sync();
+        if (lane < 3) {
+            const int m = mine - c0 < WAVE ? mine - c0 : WAVE;  // (<= 0 once this opponent's stages are done)
+            const double* vj = s_v[p][lane];
+#pragma unroll 1
+            for (int k = 0; k < m; ++k) t = __dadd_rn(t, vj[k]);
+        }
+        tel_wave_sync();  // the next chunk overwrites s_v
+    }
+    double sg = 0.0;
+    if (lane < 3) {
+        sg = __ddiv_rn(1.0, __dadd_rn(1.0, bk_exp_cr(-t)));
+        if (a.pair_raw != nullptr) a.pair_raw[(board * 4 + (size_t)p) * 3 + (size_t)lane] = t;
+    }
+    const double s1 = __shfl(sg, 1), s2 = __shfl(sg, 2);
+    if (lane == 0) a.prob[board * 4 + (size_t)p] = __ddiv_rn(__dadd_rn(__dadd_rn(sg, s1), s2), 3.0);
+    if (tid == 0) a.status[board] = (uint8_t)status;
+}
+#else
+__global__ void k_winprob_gbt(GbtArgs a);
 #endif
 
 // ------------------------------------------------------------------------------------
@@ -7034,6 +7161,11 @@ struct bk_handle_s {
     void* d_tel = nullptr;
     double tel_tab[2 * BK_TEL_TABLE] = {0};
     bool tel_tab_set = false, tel_dirty = true;
+    // bk_gbt_model_load: the resident pairwise_gbt_phase models, each one device allocation
+    // (bk_gbt_model, then the tree roots, then the nodes); id 0 marks a free slot
+    struct GbtSlot { int32_t id = 0; void* d = nullptr; size_t roots_off = 0, nodes_off = 0; };
+    GbtSlot gbt[BK_GBT_SLOTS];
+    int32_t gbt_loads = 0;  // models loaded so far: ids are (count << 3 | slot), never reused
 };
 
 static const char* const kTuneNames[BK_TUNE_COUNT] = {
@@ -7410,6 +7542,7 @@ int bk_destroy(bk_handle h) {
     if (h->own) (void)hipStreamSynchronize(h->own);
     for (Buf& b : h->buf) if (b.p) (void)hipFree(b.p);
     for (void* p : {(void*)h->d_counter, (void*)h->d_diag, h->d_tel}) if (p) (void)hipFree(p);
+    for (auto& g : h->gbt) if (g.d) (void)hipFree(g.d);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->own) (void)hipStreamDestroy(h->own);
@@ -7997,6 +8130,168 @@ int bk_winprob_eval(bk_handle h, const bk_state* states, const bk_fset* sets, in
     WinprobArgs a{{s_states.dev(), s_sets.dev(), s_turn.dev(), n, max_turns, nullptr, nullptr},
                   *model, s_prob.dev(), s_logit.dev(), s_status.dev()};
     BK_LAUNCH(h, k_winprob, dim3(n), dim3(SNAP_WAVES * WAVE), a);
+    return st.finish();
+}
+
+int bk_gbt_node_size(void) { return (int)sizeof(bk_gbt_node); }
+int bk_gbt_model_size(void) { return (int)sizeof(bk_gbt_model); }
+
+// Everything k_winprob_gbt relies on without checking it again: the ranges it indexes, and
+// child indices that grow along every path, so a walk visits at most n_nodes nodes.
+int bk_gbt_model_check(const bk_gbt_model* model, const int32_t* tree_root, int32_t n_trees, const bk_gbt_node* nodes,
+                       int32_t n_nodes, char* reason, size_t reason_len) {
+    char msg[160];
+    msg[0] = 0;
+    static const char* const kPhase[3] = {"early", "mid", "late"};
+    auto fail = [&]() {
+        if (reason && reason_len) snprintf(reason, reason_len, "%s", msg);
+        return BK_EINVAL;
+    };
+    if (!model || !tree_root || !nodes) { snprintf(msg, sizeof msg, "a null model, tree_root or nodes"); return fail(); }
+    if (n_trees < 1 || n_trees > BK_GBT_MAX_TREES) {
+        snprintf(msg, sizeof msg, "n_trees %d outside 1..%d", n_trees, BK_GBT_MAX_TREES);
+        return fail();
+    }
+    if (n_nodes < 1 || n_nodes > BK_GBT_MAX_NODES) {
+        snprintf(msg, sizeof msg, "n_nodes %d outside 1..%d", n_nodes, BK_GBT_MAX_NODES);
+        return fail();
+    }
+    for (int k = 0; k < BK_SNAPSHOT_COLUMNS; ++k) {
+        if (!__builtin_isfinite(model->mean[k]) || !__builtin_isfinite(model->scale[k])) {
+            snprintf(msg, sizeof msg, "column %d: a non-finite mean or scale", k);
+            return fail();
+        }
+        if (model->scale[k] == 0.0) { snprintf(msg, sizeof msg, "column %d: a scale of 0", k); return fail(); }
+    }
+    for (int ph = 0; ph < 3; ++ph) {
+        const bk_gbt_phase& e = model->phase[ph];
+        if (!__builtin_isfinite(e.init) || !__builtin_isfinite(e.learning_rate)) {
+            snprintf(msg, sizeof msg, "phase %s: a non-finite init or learning_rate", kPhase[ph]);
+            return fail();
+        }
+        if (e.n_trees < 1) {
+            snprintf(msg, sizeof msg, "phase %s: an empty ensemble (n_trees %d)", kPhase[ph], e.n_trees);
+            return fail();
+        }
+        if (e.first_tree < 0 || e.first_tree > n_trees || e.n_trees > n_trees - e.first_tree) {
+            snprintf(msg, sizeof msg, "phase %s: trees %d..+%d outside the %d tree roots", kPhase[ph], e.first_tree,
+                     e.n_trees, n_trees);
+            return fail();
+        }
+    }
+    for (int32_t i = 0; i < n_trees; ++i)
+        if (tree_root[i] < 0 || tree_root[i] >= n_nodes) {
+            snprintf(msg, sizeof msg, "tree %d: root %d outside the %d nodes", i, tree_root[i], n_nodes);
+            return fail();
+        }
+    for (int32_t i = 0; i < n_nodes; ++i) {
+        const bk_gbt_node& nd = nodes[i];
+        if (!__builtin_isfinite(nd.tv)) {
+            snprintf(msg, sizeof msg, "node %d: a non-finite threshold or value", i);
+            return fail();
+        }
+        if (nd.feature < 0 || nd.feature >= BK_SNAPSHOT_COLUMNS) {
+            snprintf(msg, sizeof msg, "node %d: feature %d outside 0..%d", i, nd.feature, BK_SNAPSHOT_COLUMNS - 1);
+            return fail();
+        }
+        if (nd.left == -1) continue;  // a leaf
+        if (nd.left <= i) {
+            snprintf(msg, sizeof msg, "node %d: child %d is not greater than the node's own index", i, nd.left);
+            return fail();
+        }
+        if (nd.left >= n_nodes - 1) {
+            snprintf(msg, sizeof msg, "node %d: children %d and %d outside the %d nodes", i, nd.left, nd.left + 1, n_nodes);
+            return fail();
+        }
+    }
+    return BK_OK;
+}
+
+static_assert(BK_GBT_SLOTS <= 8, "a model id keeps its slot in three bits");
+
+int bk_gbt_model_load(bk_handle h, const bk_gbt_model* model, const int32_t* tree_root, int32_t n_trees,
+                      const bk_gbt_node* nodes, int32_t n_nodes, int32_t* model_id) {
+    if (!h || !model_id) return set_err(h, BK_EINVAL, "bk_gbt_model_load: invalid arguments%s", "");
+    *model_id = 0;
+    char why[160];
+    if (bk_gbt_model_check(model, tree_root, n_trees, nodes, n_nodes, why, sizeof why) != BK_OK)
+        return set_err(h, BK_EINVAL, "bk_gbt_model_load: %s", why);
+    int slot = -1;
+    for (int i = BK_GBT_SLOTS - 1; i >= 0; --i)
+        if (!h->gbt[i].id) slot = i;
+    if (slot < 0 || h->gbt_loads >= (INT32_MAX >> 3))
+        return set_err(h, BK_EOVERFLOW, "bk_gbt_model_load: all model slots are in use (bk_gbt_model_free one)%s", "");
+    HIPCHK(h, hipSetDevice(h->device));
+    const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t roots_off = up16(sizeof(bk_gbt_model));
+    const size_t nodes_off = roots_off + up16(sizeof(int32_t) * (size_t)n_trees);
+    const size_t bytes = nodes_off + sizeof(bk_gbt_node) * (size_t)n_nodes;
+    std::vector<char> img(bytes, 0);
+    memcpy(img.data(), model, sizeof(bk_gbt_model));
+    memcpy(img.data() + roots_off, tree_root, sizeof(int32_t) * (size_t)n_trees);
+    memcpy(img.data() + nodes_off, nodes, sizeof(bk_gbt_node) * (size_t)n_nodes);
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(h, BK_ENOMEM, "bk_gbt_model_load: no device memory for the model%s", "");
+    }
+    const hipError_t e = hipMemcpy(d, img.data(), bytes, hipMemcpyHostToDevice);  // complete on return
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return set_err(h, BK_EHIP, "bk_gbt_model_load: hipMemcpy: %s", hipGetErrorString(e));
+    }
+    h->gbt_loads += 1;
+    h->gbt[slot] = {(int32_t)((h->gbt_loads << 3) | slot), d, roots_off, nodes_off};
+    *model_id = h->gbt[slot].id;
+    return BK_OK;
+}
+
+// the slot of a live model id, or null
+static bk_handle_s::GbtSlot* gbt_slot(bk_handle h, int32_t model_id) {
+    if (model_id <= 0 || (model_id & 7) >= BK_GBT_SLOTS) return nullptr;
+    bk_handle_s::GbtSlot* g = &h->gbt[model_id & 7];
+    return g->id == model_id ? g : nullptr;
+}
+
+int bk_gbt_model_free(bk_handle h, int32_t model_id) {
+    if (!h) return BK_EINVAL;
+    bk_handle_s::GbtSlot* g = gbt_slot(h, model_id);
+    if (!g) return set_err(h, BK_EINVAL, "bk_gbt_model_free: unknown or freed model_id%s", "");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->busy) HIPCHK(h, hipStreamSynchronize(h->busy_stream));
+    HIPCHK(h, hipStreamSynchronize(h->cur));  // no launch still reads the model
+    HIPCHK(h, hipFree(g->d));
+    *g = bk_handle_s::GbtSlot{};
+    return BK_OK;
+}
+
+int bk_winprob_eval_gbt(bk_handle h, const bk_state* states, const bk_fset* sets, int32_t n, const int32_t* turn_index,
+                        int32_t max_turns, int32_t model_id, double* prob, double* pair_raw, uint8_t* status, int mem) {
+    if (!h || !states || !sets || !prob || !status || n < 0 || (mem != BK_MEM_HOST && mem != BK_MEM_DEVICE))
+        return set_err(h, BK_EINVAL, "bk_winprob_eval_gbt: invalid arguments%s", "");
+    if (max_turns < 0) return set_err(h, BK_EINVAL, "bk_winprob_eval_gbt: max_turns must be >= 0%s", "");
+    if (mem == BK_MEM_DEVICE && (((uintptr_t)sets & 15) || ((uintptr_t)states & 7) || ((uintptr_t)prob & 7) ||
+                                 ((uintptr_t)pair_raw & 7) || ((uintptr_t)turn_index & 3)))
+        return set_err(h, BK_EINVAL, "bk_winprob_eval_gbt: sets must be 16-byte, states, prob and pair_raw 8-byte, "
+                                     "turn_index 4-byte aligned%s", "");
+    const bk_handle_s::GbtSlot* g = gbt_slot(h, model_id);
+    if (!g) return set_err(h, BK_EINVAL, "bk_winprob_eval_gbt: unknown or freed model_id%s", "");
+    if (n == 0) return BK_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    BK_IDLE(h, "bk_winprob_eval_gbt");
+    Staging st(h, mem);
+    const auto s_states = st.in(states, sizeof(bk_state) * (size_t)n);
+    const auto s_sets = st.in(sets, sizeof(bk_fset) * (size_t)n);
+    const auto s_turn = st.in(turn_index, sizeof(int32_t) * (size_t)n);
+    const auto s_prob = st.out(prob, sizeof(double) * 4 * (size_t)n);
+    const auto s_raw = st.out(pair_raw, sizeof(double) * 12 * (size_t)n);
+    const auto s_status = st.out(status, (size_t)n);
+    if (int rc = st.commit()) return rc;
+    const char* base = (const char*)g->d;
+    GbtArgs a{{s_states.dev(), s_sets.dev(), s_turn.dev(), n, max_turns, nullptr, nullptr},
+              (const bk_gbt_model*)base, (const int32_t*)(base + g->roots_off), (const GbtNode*)(base + g->nodes_off),
+              s_prob.dev(), s_raw.dev(), s_status.dev()};
+    BK_LAUNCH(h, k_winprob_gbt, dim3(n), dim3(SNAP_WAVES * WAVE), a);
     return st.finish();
 }
 

@@ -232,6 +232,48 @@ class BlokusGPU:
         status uint8 [n] of N.SNAP_ST_* bits: check it before trusting prob).  Torch cuda in
         gives torch cuda out."""
         native = model if isinstance(model, N.BkWinprobModel) else model.as_native()
+
+        def launch(states_ptr, sets_ptr, n, turn_ptr, prob_ptr, pair_ptr, status_ptr, mem):
+            self.handle.winprob_eval(states_ptr, sets_ptr, n, turn_ptr, max_turns, native, prob_ptr, pair_ptr,
+                                     status_ptr, mem)
+        return self._winprob_launch(states, sets, turn_index, pair_logits, launch)
+
+    def winprob_eval_gbt(self, states, sets, turn_index, max_turns: int, model, *, pair_raw: bool = False):
+        """winprob_eval for a pairwise_gbt_phase model (bk_winprob_eval_gbt, k_winprob_gbt):
+        model a mcts.learned_evaluator.GbtPhaseModel (anything with ``key()`` and
+        ``as_native()`` giving (N.BkGbtModel, tree roots, nodes)).  The model is uploaded on
+        its first use and stays in one of the handle's N.GBT_SLOTS slots, found again by its
+        value key; when the slots are full the least recently used model is freed.  Returns
+        (prob, pair_raw float64 [n, 4, 3] or None -- the ensembles' raw scores --, status)."""
+        model_id = self.gbt_model_id(model)
+
+        def launch(states_ptr, sets_ptr, n, turn_ptr, prob_ptr, pair_ptr, status_ptr, mem):
+            self.handle.winprob_eval_gbt(states_ptr, sets_ptr, n, turn_ptr, max_turns, model_id, prob_ptr, pair_ptr,
+                                         status_ptr, mem)
+        return self._winprob_launch(states, sets, turn_index, pair_raw, launch)
+
+    def gbt_model_id(self, model) -> int:
+        """The id of `model`'s resident copy on this handle, uploading it if need be."""
+        ids = self.__dict__.setdefault("_gbt_ids", {})  # value key -> id, least recently used first
+        key = model.key()
+        model_id = ids.pop(key, None)
+        if model_id is None:
+            if len(ids) >= N.GBT_SLOTS:
+                oldest = next(iter(ids))
+                self.handle.gbt_model_free(ids.pop(oldest))
+            model_id = self.handle.gbt_model_load(*model.as_native())
+        ids[key] = model_id
+        return model_id
+
+    def gbt_model_release(self, model) -> bool:
+        """Free `model`'s resident copy, if there is one (bk_gbt_model_free)."""
+        model_id = self.__dict__.get("_gbt_ids", {}).pop(model.key(), None)
+        if model_id is not None:
+            self.handle.gbt_model_free(model_id)
+        return model_id is not None
+
+    def _winprob_launch(self, states, sets, turn_index, pairs: bool, launch):
+        """The buffers of one learned-evaluator launch, host or torch cuda, around `launch`."""
         if _is_torch(states):
             import torch
             n = states.shape[0]
@@ -240,13 +282,11 @@ class BlokusGPU:
             if turn_index is not None:
                 _check_device_tensor(turn_index, "turn_index", torch.int32, (n,), self.device)
             prob = torch.empty((n, 4), dtype=torch.float64, device=states.device)
-            logit = torch.empty((n, 4, 3), dtype=torch.float64, device=states.device) if pair_logits else None
+            logit = torch.empty((n, 4, 3), dtype=torch.float64, device=states.device) if pairs else None
             status = torch.empty((n,), dtype=torch.uint8, device=states.device)
             self._stream_from_torch()
-            self.handle.winprob_eval(states.data_ptr(), sets.data_ptr(), n,
-                                     turn_index.data_ptr() if turn_index is not None else 0, max_turns, native,
-                                     prob.data_ptr(), logit.data_ptr() if pair_logits else 0, status.data_ptr(),
-                                     N.MEM_DEVICE)
+            launch(states.data_ptr(), sets.data_ptr(), n, turn_index.data_ptr() if turn_index is not None else 0,
+                   prob.data_ptr(), logit.data_ptr() if pairs else 0, status.data_ptr(), N.MEM_DEVICE)
             return prob, logit, status
         st = np.ascontiguousarray(states).view(np.uint8)
         fs = np.ascontiguousarray(sets).view(np.uint8)
@@ -258,12 +298,11 @@ class BlokusGPU:
             if ti.shape[0] != n:
                 raise ValueError(f"turn_index: {ti.shape[0]} entries for {n} boards")
         prob = np.zeros((n, 4), dtype=np.float64)
-        logit = np.zeros((n, 4, 3), dtype=np.float64) if pair_logits else None
+        logit = np.zeros((n, 4, 3), dtype=np.float64) if pairs else None
         status = np.zeros(n, dtype=np.uint8)
         self.handle.set_stream(None)
-        self.handle.winprob_eval(st.ctypes.data, fs.ctypes.data, n, ti.ctypes.data if ti is not None else 0, max_turns,
-                                 native, prob.ctypes.data, logit.ctypes.data if pair_logits else 0, status.ctypes.data,
-                                 N.MEM_HOST)
+        launch(st.ctypes.data, fs.ctypes.data, n, ti.ctypes.data if ti is not None else 0, prob.ctypes.data,
+               logit.ctypes.data if pairs else 0, status.ctypes.data, N.MEM_HOST)
         return prob, logit, status
 
     def step_metrics(self, before, sets_before, after, sets_after, steps):

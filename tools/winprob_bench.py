@@ -13,7 +13,11 @@ also times bk_telemetry (stability on, k = 3) on the same tensors in the same pr
 the launches of the two kernels alternating.  --eval times bk_winprob_eval instead (the
 learned evaluator, k_winprob: device pointers, no pair logits; the model from --model),
 alternating with bk_snapshot_features writing the rows only, and reports both medians and
-their ratio.
+their ratio.  --gbt times bk_winprob_eval_gbt (k_winprob_gbt, a pairwise_gbt_phase model)
+alternating with bk_winprob_eval on the same tensors, once per entry of --gbt-stages: the
+model of --gbt-model as it is (40 stages per phase in the fixture), or with every ensemble's
+trees repeated up to that many stages, so the cost per stage shows.  One JSON line per entry,
+appended to --out when given.
 
 The comparison point is the reference's build_snapshot_runtime_context +
 extract_player_snapshot_features for the four players on one CPU core over the same ply
@@ -94,6 +98,64 @@ def eval_bench(gpu, args, d_st, d_fs, d_ti, n) -> dict:
             "prob_finite": bool(np.isfinite(prob).all()), "prob_mean": float(prob.mean())}
 
 
+def stretched(model, stages):
+    """`model` with every ensemble's trees repeated (whole copies of its node array) until it
+    has `stages` stages; the learning rate shrinks alike, so the scores stay in range."""
+    from reinforcementlearning_blokus_amd.mcts.learned_evaluator import GbtEnsemble, GbtPhaseModel
+    out = []
+    for e in model.ensembles:
+        reps = -(-stages // len(e.roots))
+        n = len(e.tv)
+        roots = [r + k * n for k in range(reps) for r in e.roots][:stages]
+        left = [lf if lf == -1 else lf + k * n for k in range(reps) for lf in e.left]
+        out.append(GbtEnsemble(e.init, e.learning_rate * len(e.roots) / stages, roots, left, e.feature * reps, e.tv * reps))
+    return GbtPhaseModel(out, model.phase_ensemble, model.mean, model.scale, model.feature_columns)
+
+
+def gbt_bench(gpu, args, d_st, d_fs, d_ti, n) -> list:
+    """bk_winprob_eval_gbt and bk_winprob_eval (device pointers, no pair outputs) alternating in
+    this process on the same tensors; each launch timed by the library's HIP events."""
+    import torch
+
+    from reinforcementlearning_blokus_amd.mcts.learned_evaluator import GbtPhaseModel, WinProbModel
+    with open(args.model) as fh:
+        doc = json.load(fh)
+    logreg = WinProbModel.from_dict(doc.get("model", doc))
+    with open(args.gbt_model) as fh:
+        doc = json.load(fh)
+    base = GbtPhaseModel.from_dict(doc["models"]["phases"] if "models" in doc else doc)
+    lines = []
+    for stages in args.gbt_stages:
+        model = base if all(len(e.roots) == stages for e in base.ensembles) else stretched(base, stages)
+        gbt_ms, lr_ms = [], []
+        for i in range(args.warmup + args.launches):
+            _, _, _ = gpu.winprob_eval(d_st, d_fs, d_ti, 2500, logreg)
+            gpu.synchronize()
+            assert gpu.last_kernel() == "k_winprob"
+            if i >= args.warmup:
+                lr_ms.append(gpu.last_kernel_ms())
+            prob, _, status = gpu.winprob_eval_gbt(d_st, d_fs, d_ti, 2500, model)
+            gpu.synchronize()
+            assert gpu.last_kernel() == "k_winprob_gbt"
+            if i >= args.warmup:
+                gbt_ms.append(gpu.last_kernel_ms())
+        torch.cuda.synchronize()
+        prob = prob.cpu().numpy()
+        gmed, lmed = statistics.median(gbt_ms), statistics.median(lr_ms)
+        lines.append({"tool": "winprob_bench", "mode": "gbt", "boards": n, "min_ply": args.min_ply,
+                      "max_ply": args.max_ply, "warmup": args.warmup, "launches": len(gbt_ms), "stages": stages,
+                      "nodes": sum(len(e.tv) for e in model.ensembles), "ensembles": len(model.ensembles),
+                      "gbt_ms_median": gmed, "gbt_ms_min": min(gbt_ms), "gbt_ms_max": max(gbt_ms),
+                      "gbt_spread_rel": (max(gbt_ms) - min(gbt_ms)) / (2 * gmed),
+                      "logreg_ms_median": lmed, "logreg_ms_min": min(lr_ms), "logreg_ms_max": max(lr_ms),
+                      "logreg_spread_rel": (max(lr_ms) - min(lr_ms)) / (2 * lmed),
+                      "gbt_over_logreg": gmed / lmed, "boards_per_s": n / (gmed * 1e-3),
+                      "evaluations_per_s": 4 * n / (gmed * 1e-3),
+                      "status_nonzero": int(status.cpu().numpy().astype(bool).sum()),
+                      "prob_finite": bool(np.isfinite(prob).all()), "prob_mean": float(prob.mean())})
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--boards", type=int, default=4096)
@@ -107,6 +169,12 @@ def main():
                     help="time bk_winprob_eval (no pair logits) alternating with bk_snapshot_features (rows only)")
     ap.add_argument("--model", metavar="JSON", default=os.path.join(ROOT, "tests", "golden", "winprob_eval.json"),
                     help="--eval: a WinProbModel JSON document, or a fixture holding one under \"model\"")
+    ap.add_argument("--gbt", action="store_true",
+                    help="time bk_winprob_eval_gbt alternating with bk_winprob_eval, once per --gbt-stages entry")
+    ap.add_argument("--gbt-model", metavar="JSON", default=os.path.join(ROOT, "tests", "golden", "winprob_gbt.json"),
+                    help="--gbt: a GbtPhaseModel JSON document, or a fixture holding one under models.phases")
+    ap.add_argument("--gbt-stages", type=int, nargs="+", default=[40, 400])
+    ap.add_argument("--out", metavar="JSONL", help="--gbt: also append the lines to this file")
     ap.add_argument("--cpu-reference", metavar="PATH", help="time the reference checkout at PATH on the CPU instead")
     ap.add_argument("--cpu-calls", type=int, default=33)
     args = ap.parse_args()
@@ -138,6 +206,13 @@ def main():
     d_ti = torch.from_numpy(states["move_count"].astype(np.int32)).to(dev)
     if args.eval:
         print(json.dumps(eval_bench(gpu, args, d_st, d_fs, d_ti, n)), flush=True)
+        return
+    if args.gbt:
+        for line in gbt_bench(gpu, args, d_st, d_fs, d_ti, n):
+            print(json.dumps(line), flush=True)
+            if args.out:
+                with open(args.out, "a") as fh:
+                    fh.write(json.dumps(line) + "\n")
         return
     ms, tel_ms = [], []
     for i in range(args.warmup + args.launches):
