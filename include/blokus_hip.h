@@ -573,6 +573,7 @@ int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const 
 #define BK_DIAG_K_COOP 3      /* k_mcts_coop */
 #define BK_DIAG_K_COOP_H 4    /* k_mcts_coop_h */
 #define BK_DIAG_K_COOP_L 5    /* k_mcts_coop_l (bk_mcts_learned) */
+#define BK_DIAG_K_COOP_G 6    /* k_mcts_coop_g (bk_mcts_learned_gbt) */
 int bk_debug_mcts_failure(bk_handle h, uint32_t* out, int32_t n);
 
 /*
@@ -842,6 +843,31 @@ int bk_mcts_learned(bk_handle h, const bk_state* roots, const bk_fset* root_sets
                     int32_t* tt_count, const double* log_table, int32_t log_len, const bk_winprob_model* model,
                     int32_t max_turns, double bias_weight, double* prior_bias, int32_t* bias_updates,
                     bk_mcts_node* nodes, double* rewards, uint8_t* hit_flags, bk_mcts_out* out, int mem);
+
+/*
+ * bk_mcts_learned_gbt -- bk_mcts_learned for a pairwise_gbt_phase model, whole in one launch
+ * (k_mcts_coop_g, one wave per search; added within ABI 7: new symbols only).  The arguments
+ * are bk_mcts_learned's with `model_id`, a resident model of this handle (bk_gbt_model_load),
+ * in place of the model pointer; the search, the TT, progressive bias, bias_updates, the
+ * iter_stop / resume chunks and `out` are bk_mcts_learned's.  A node's board is evaluated
+ * exactly as bk_winprob_eval_gbt evaluates it (turn_index = move_count = the root's move_count
+ * + depth, `max_turns`): the reward equals bk_winprob_eval_gbt's prob for that board bit for
+ * bit, whichever phase's ensemble the board's occupancy selects.  cfg->flags must be 0.
+ * The launch is synchronous: the call returns after the kernel, so bk_gbt_model_free, which
+ * waits for the stream, never takes a model from under a search.
+ * BK_EINVAL before any GPU work: a model_id that was never returned or has been freed, a
+ * non-finite bias weight, max_turns < 0, cfg->flags != 0, and bk_mcts_learned's rules for the
+ * buffers (a null required pointer, node_cap < 1, a tt_cap that is no power of two,
+ * log_len < 1); n_games == 0 is BK_OK without a launch.  An invalid board inside a search (a
+ * non-zero snapshot status) sets BK_MCTS_EINTERNAL.  The failure record is bk_mcts's, with
+ * BK_DIAG_K_COOP_G; bk_last_kernel names "k_mcts_coop_g".
+ */
+int bk_mcts_learned_gbt(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const uint8_t* players,
+                        const uint64_t* root_hash, int32_t n_games, const bk_mcts_cfg* cfg, const uint64_t* zobrist,
+                        int32_t n_zobrist, const int32_t* zobrist_index, uint64_t* tt_keys, double* tt_vals,
+                        int32_t* tt_count, const double* log_table, int32_t log_len, int32_t model_id,
+                        int32_t max_turns, double bias_weight, double* prior_bias, int32_t* bias_updates,
+                        bk_mcts_node* nodes, double* rewards, uint8_t* hit_flags, bk_mcts_out* out, int mem);
 
 /*
  * bk_step_metrics -- the integers behind one line of the strategy step log

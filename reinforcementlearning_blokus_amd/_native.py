@@ -44,10 +44,12 @@ EXPORTS = (
     "bk_mcts_learned",
     "bk_gbt_node_size", "bk_gbt_model_size", "bk_gbt_model_check", "bk_gbt_model_load", "bk_gbt_model_free",
     "bk_winprob_eval_gbt",
+    "bk_mcts_learned_gbt",
 )
 # bk_debug_mcts_failure record (include/blokus_hip.h BK_DIAG_*)
 DIAG_WORDS = 64
-DIAG_KERNELS = ("k_mcts", "k_mcts_pair", "k_mcts_h", "k_mcts_coop", "k_mcts_coop_h", "k_mcts_coop_l")
+DIAG_KERNELS = ("k_mcts", "k_mcts_pair", "k_mcts_h", "k_mcts_coop", "k_mcts_coop_h", "k_mcts_coop_l",
+                "k_mcts_coop_g")
 # bk_set_tuning keys (include/blokus_hip.h BK_TUNE_*), by the environment variable name
 # bk_create reads each from once
 TUNE_KEYS = {name: i for i, name in enumerate((
@@ -359,6 +361,9 @@ def load():
             "bk_gbt_model_load": (C.c_int, [vp, P(BkGbtModel), vp, C.c_int32, vp, C.c_int32, P(C.c_int32)]),
             "bk_gbt_model_free": (C.c_int, [vp, C.c_int32]),
             "bk_winprob_eval_gbt": (C.c_int, [vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int]),
+            "bk_mcts_learned_gbt": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, P(BkMctsCfg), vp, C.c_int32, vp, vp, vp,
+                                              vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp,
+                                              vp, vp, C.c_int]),
         }
         for name, (res, args) in sigs.items():
             f = getattr(L, name)
@@ -706,6 +711,19 @@ class Handle:
                                          float(bias_weight), v(prior_ptr), v(bias_updates_ptr), v(nodes_ptr),
                                          v(rewards_ptr), v(flags_ptr), v(out_ptr), mem)
         self.check(rc, "bk_mcts_learned")
+
+    def mcts_learned_gbt(self, roots_ptr, sets_ptr, players_ptr, hash_ptr, n_games, cfg: BkMctsCfg, zob_ptr, n_zob,
+                         zidx_ptr, ttk_ptr, ttv_ptr, ttc_ptr, log_ptr, log_len, model_id, max_turns,
+                         bias_weight, prior_ptr, bias_updates_ptr, nodes_ptr, rewards_ptr, flags_ptr, out_ptr, mem):
+        """bk_mcts_learned_gbt: mcts_learned with a resident model's id (gbt_model_load) as the model."""
+        v = lambda x: C.c_void_p(x or 0)  # noqa: E731
+        with self._lock:
+            rc = self._L.bk_mcts_learned_gbt(self._h, v(roots_ptr), v(sets_ptr), v(players_ptr), v(hash_ptr),
+                                             n_games, C.byref(cfg), v(zob_ptr), n_zob, v(zidx_ptr), v(ttk_ptr),
+                                             v(ttv_ptr), v(ttc_ptr), v(log_ptr), log_len, int(model_id),
+                                             int(max_turns), float(bias_weight), v(prior_ptr), v(bias_updates_ptr),
+                                             v(nodes_ptr), v(rewards_ptr), v(flags_ptr), v(out_ptr), mem)
+        self.check(rc, "bk_mcts_learned_gbt")
 
     def arena_advance(self, states_ptr, sets_ptr, n, cfg: BkRolloutCfg, masks_ptr, rng_ptr, out_ptr, mem):
         with self._lock:

@@ -75,6 +75,7 @@
 #define BK_U_ROLLOUT_FRHS 15
 #define BK_U_COOP_L 16
 #define BK_U_GBT 17
+#define BK_U_COOP_G 18
 #ifndef BK_TU
 #define BK_TU 0
 #endif
@@ -6249,7 +6250,7 @@ struct WinprobArgs {
 static_assert(sizeof(bk_snapshot_rec) == 80 && sizeof(bk_snapshot_rec) % 8 == 0, "the record is copied out as dwords");
 static_assert(BK_SNAPSHOT_COLUMNS <= WAVE, "one lane per column");
 
-#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L) || BK_DEF(BK_U_GBT)
+#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L) || BK_DEF(BK_U_GBT) || BK_DEF(BK_U_COOP_G)
 // O_i (distinct orientations), S_i (cells) and the pieces of each size, from the orientation table
 struct SnapTab {
     uint8_t orients[BK_PIECES], size[BK_PIECES];
@@ -6563,7 +6564,7 @@ __global__ __launch_bounds__(SNAP_WAVES * WAVE) void k_snapshot(SnapArgs a) {
 // 172 on the edge boards 2 ulp from CPython's.  It overflows to +inf (s = 0) and underflows
 // to 0 (s = 1) for very large |t|.
 #endif  // BK_DEF(BK_U_SNAPSHOT)
-#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L) || BK_DEF(BK_U_GBT)
+#if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L) || BK_DEF(BK_U_GBT) || BK_DEF(BK_U_COOP_G)
 #include "exp_cr.h"
 #endif
 #if BK_DEF(BK_U_SNAPSHOT) || BK_DEF(BK_U_COOP_L)
@@ -6761,26 +6762,20 @@ struct LeafArgs {
     int32_t* bias_updates;  // n: progressive-bias updates per search
 };
 
-#if BK_DEF(BK_U_COOP_L)
-struct LeafScratch {
-    double feat[4][BK_SNAPSHOT_COLUMNS];
-    double u[3][BK_SNAPSHOT_COLUMNS];
-    double norm[BK_PIECES], wt[BK_PIECES];
-    uint32_t fr[4][20], pc[4][BK_PIECES];
-    uint32_t mob[4], fsz[4], cdist[4], adj[4], own_cells[4];
-    uint32_t status;
-};
-static_assert(COOP_ML_DWORD * 4 + sizeof(LeafScratch) <= COOP_AREA * 4, "the evaluation's scratch fits a wave's area");
-
-struct LeafEval {
-    const LeafArgs& la;
+#if BK_DEF(BK_U_COOP_L) || BK_DEF(BK_U_COOP_G)
+// The feature pass of both in-search evaluators (LeafEval, GbtLeafEval): the launch's
+// arguments `la` (max_turns) and a Scratch that holds feat, norm, wt, fr, pc, the per-player
+// scalars and status, behind COOP_ML_DWORD in the wave's area.
+template <typename Args, typename Scratch>
+struct LeafFeatures {
+    const Args& la;
 
     // The four feature rows of the board in slab / T (used pieces and first-move flags from
     // m) into the wave's scratch.  Returns the snapshot status bits (0 = a valid board).
     __device__ __forceinline__ uint32_t features(const Slab& slab, const bk_fset& T, const Mc& m, int ply, uint32_t* my,
                                                  int16_t* otab, int lane) const {
 #pragma clang fp contract(off)
-        LeafScratch& S = *reinterpret_cast<LeafScratch*>(my + COOP_ML_DWORD);
+        Scratch& S = *reinterpret_cast<Scratch*>(my + COOP_ML_DWORD);
         uint2* rows = reinterpret_cast<uint2*>(my) + lane;
         tel_wave_sync();  // the placement's stores to the slab and the tables are visible
         for (int i = lane; i < 4 * 20; i += WAVE) (&S.fr[0][0])[i] = 0u;
@@ -6852,7 +6847,21 @@ struct LeafEval {
         }
         return S.status;
     }
+};
+#endif
 
+#if BK_DEF(BK_U_COOP_L)
+struct LeafScratch {
+    double feat[4][BK_SNAPSHOT_COLUMNS];
+    double u[3][BK_SNAPSHOT_COLUMNS];
+    double norm[BK_PIECES], wt[BK_PIECES];
+    uint32_t fr[4][20], pc[4][BK_PIECES];
+    uint32_t mob[4], fsz[4], cdist[4], adj[4], own_cells[4];
+    uint32_t status;
+};
+static_assert(COOP_ML_DWORD * 4 + sizeof(LeafScratch) <= COOP_AREA * 4, "the evaluation's scratch fits a wave's area");
+
+struct LeafEval : LeafFeatures<LeafArgs, LeafScratch> {
     // Player p's win probability from the rows features() left (uniform over the wave)
     __device__ __forceinline__ double value(int p, uint32_t* my, int lane) const {
 #pragma clang fp contract(off)
@@ -6871,10 +6880,127 @@ struct LeafEval {
 };
 
 __global__ __launch_bounds__(COOP_WAVES * WAVE) void k_mcts_coop_l(MctsArgs a, LeafArgs la) {
-    mcts_coop_body<false, true>(a, LeafEval{la});
+    mcts_coop_body<false, true>(a, LeafEval{{la}});
 }
 #else
 __global__ void k_mcts_coop_l(MctsArgs a, LeafArgs la);
+#endif
+
+// ------------------------------------------------------------------------------------
+// k_mcts_coop_g: k_mcts_coop_l for a pairwise_gbt_phase model (bk_mcts_learned_gbt).  The
+// search and the feature pass are k_mcts_coop_l's; value() is k_winprob_gbt's arithmetic in
+// the search's one wave, on the rows features() left: lane k < 34 forms the three float32
+// inputs xf_k, each pair's phase comes from the two rows' occupancy column, lane l walks
+// stage 64 c + l for the three opponents (three 16-byte node loads in flight per step) and
+// leaves lr * leaf in LDS, and after the wave's sync lane j < 3 continues opponent j's sum
+// in stage order.  The product and the add stay in different lanes with LDS between them
+// (beside each other they fuse into one v_fmac_f64: not sklearn's value), so a value equals
+// bk_winprob_eval_gbt's for the same board bit for bit.  The model is the handle's resident
+// copy in device memory; bk_gbt_model_check, at its load, is what bounds every walk and
+// index -- nothing is checked again here.
+// LDS: GbtLeafScratch after the rows' 40 dwords per lane, where LeafScratch sits.
+// ------------------------------------------------------------------------------------
+struct GbtLeafArgs {
+    const bk_gbt_model* m;  // device memory (the handle's slot), as GbtArgs carries it
+    const int32_t* roots;
+    const GbtNode* nodes;
+    int32_t max_turns;
+    double bias_w;          // progressive_bias_weight, 0 = no progressive bias
+    double* prior;          // n x node_cap prior_bias entries (bias_w != 0)
+    int32_t* bias_updates;  // n: progressive-bias updates per search
+};
+
+#if BK_DEF(BK_U_COOP_G)
+struct GbtLeafScratch {
+    double feat[4][BK_SNAPSHOT_COLUMNS];
+    double v[3][WAVE];  // a chunk's lr * leaf values
+    double norm[BK_PIECES], wt[BK_PIECES];
+    float x[3][BK_SNAPSHOT_COLUMNS];
+    uint32_t fr[4][20], pc[4][BK_PIECES];
+    uint32_t mob[4], fsz[4], cdist[4], adj[4], own_cells[4];
+    uint32_t status;
+};
+static_assert(COOP_ML_DWORD * 4 + sizeof(GbtLeafScratch) <= COOP_AREA * 4, "the evaluation's scratch fits a wave's area");
+
+struct GbtLeafEval : LeafFeatures<GbtLeafArgs, GbtLeafScratch> {
+    // Player p's win probability from the rows features() left (uniform over the wave)
+    __device__ __forceinline__ double value(int p, uint32_t* my, int lane) const {
+#pragma clang fp contract(off)
+        GbtLeafScratch& S = *reinterpret_cast<GbtLeafScratch*>(my + COOP_ML_DWORD);
+        const bk_gbt_model* M = la.m;
+        if (lane < BK_SNAPSHOT_COLUMNS) {
+            const double fp = S.feat[p][lane], mean = M->mean[lane], scale = M->scale[lane];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int q = j + (j >= p ? 1 : 0);
+                const double x = __dsub_rn(fp, S.feat[q][lane]);
+                S.x[j][lane] = __double2float_rn(__ddiv_rn(__dsub_rn(x, mean), scale));
+            }
+        }
+        // each pair's ensemble (wave-uniform): the phase of the pair's mean occupancy
+        int first[3], cnt[3], nmax = 0;
+        double lr[3];
+        double t = 0.0;  // lane j < 3: opponent j's running sum
+        int mine = 0;    // lane j < 3: opponent j's stage count
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int q = j + (j >= p ? 1 : 0);
+            const double occ = __ddiv_rn(__dadd_rn(S.feat[p][GBT_OCC_COLUMN], S.feat[q][GBT_OCC_COLUMN]), 2.0);
+            const int ph = __builtin_amdgcn_readfirstlane(occ < 0.33 ? 0 : (occ < 0.66 ? 1 : 2));
+            const bk_gbt_phase& e = M->phase[ph];
+            first[j] = e.first_tree;
+            cnt[j] = e.n_trees;
+            nmax = cnt[j] > nmax ? cnt[j] : nmax;
+            lr[j] = e.learning_rate;
+            if (lane == j) { t = e.init; mine = e.n_trees; }
+        }
+        tel_wave_sync();  // the wave's xf are complete
+        for (int c0 = 0; c0 < nmax; c0 += WAVE) {  // (uniform)
+            const int stage = c0 + lane;
+            int node[3];
+            double v[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int j = 0; j < 3; ++j) node[j] = stage < cnt[j] ? la.roots[first[j] + stage] : -1;
+            while (node[0] >= 0 || node[1] >= 0 || node[2] >= 0) {
+                GbtNode nd[3];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) nd[j] = la.nodes[node[j] >= 0 ? node[j] : 0];  // three loads in flight
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    if (node[j] < 0) continue;
+                    if (nd[j].left < 0) {
+                        v[j] = nd[j].tv;
+                        node[j] = -1;
+                    } else {
+                        node[j] = nd[j].left + ((double)S.x[j][nd[j].feature] <= nd[j].tv ? 0 : 1);
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (stage < cnt[j]) S.v[j][lane] = __dmul_rn(lr[j], v[j]);
+            tel_wave_sync();
+            if (lane < 3) {
+                const int n = mine - c0 < WAVE ? mine - c0 : WAVE;  // (<= 0 once this opponent's stages are done)
+                const double* vj = S.v[lane];
+#pragma unroll 1
+                for (int k = 0; k < n; ++k) t = __dadd_rn(t, vj[k]);
+            }
+            tel_wave_sync();  // the next chunk overwrites v
+        }
+        double sg = 0.0;
+        if (lane < 3) sg = __ddiv_rn(1.0, __dadd_rn(1.0, bk_exp_cr(-t)));
+        const double s0 = lane_bcast(sg, 0), s1 = lane_bcast(sg, 1), s2 = lane_bcast(sg, 2);
+        tel_wave_sync();  // x is free for the next call
+        return __ddiv_rn(__dadd_rn(__dadd_rn(s0, s1), s2), 3.0);
+    }
+};
+
+__global__ __launch_bounds__(COOP_WAVES * WAVE) void k_mcts_coop_g(MctsArgs a, GbtLeafArgs ga) {
+    mcts_coop_body<false, true>(a, GbtLeafEval{{ga}});
+}
+#else
+__global__ void k_mcts_coop_g(MctsArgs a, GbtLeafArgs ga);
 #endif
 
 // ------------------------------------------------------------------------------------
@@ -8686,6 +8812,60 @@ int bk_mcts(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const 
     return c.finish("bk_mcts: step guard tripped%s");
 }
 
+// What bk_mcts_learned and bk_mcts_learned_gbt do alike once each has judged its model: the
+// buffer and game checks, the staging with the prior_bias and bias_updates sections, the
+// grid and the step bound of a one-wave-per-search launch, and MctsArgs (armed, with
+// `kernel_id`); cfg_msg and game_msg are the entry point's messages for those checks.  The
+// caller builds its evaluator's arguments around L.prior / L.bias and launches its kernel
+// on L.blocks blocks.
+struct LearnedLaunch {
+    MctsArgs a;
+    int blocks;
+    double* prior;
+    int32_t* bias;
+};
+static int learned_prepare(MctsCall& c, double bias_weight, double* prior_bias, int32_t* bias_updates,
+                           uint32_t kernel_id, const char* cfg_msg, const char* game_msg, LearnedLaunch& L) {
+    bk_handle h = c.h;
+    const bk_mcts_cfg* cfg = c.cfg;
+    const int32_t n_games = c.n_games;
+    int rc = c.check_buffers(!bias_updates || (bias_weight != 0.0 && !prior_bias), cfg->flags != 0, cfg_msg);
+    if (rc) return rc;
+    rc = c.check_games([](int32_t) { return false; }, game_msg);
+    if (rc) return rc;
+    if ((rc = c.stage())) return rc;
+    const size_t n = (size_t)n_games;
+    const auto s_prior = c.st.add(bias_weight != 0.0 ? prior_bias : nullptr, sizeof(double) * (size_t)cfg->node_cap * n, c.io);
+    const auto s_bias = c.st.add(bias_updates, sizeof(int32_t) * n, c.io);
+    if ((rc = c.commit())) return rc;
+    // persistent grid of COOP_WAVES-search blocks; the search's McLane and slab live in LDS
+    // (DESIGN.md 4 has the kernels' resources)
+    int coop_bpc = 3;  // by LDS: 48 KB per block
+    if (tune_or(h, BK_TUNE_COOP_BLOCKS_PER_CU, 0) > 0) coop_bpc = (int)h->tune[BK_TUNE_COOP_BLOCKS_PER_CU];
+    int blocks = h->num_cu * coop_bpc;
+    const int need = (int)(((int64_t)n_games + COOP_WAVES - 1) / COOP_WAVES);
+    if (blocks > need) blocks = need;
+    if (blocks < 1) blocks = 1;
+    const uint32_t nslots = (uint32_t)blocks * COOP_WAVES;
+    const uint64_t per_wave = ((uint64_t)n_games + nslots - 1) / nslots + 1;
+    const uint64_t steps = 2 * per_wave * ((uint64_t)cfg->iterations + 1) * 3 + 64;  // one movegen per iteration
+    bk_mcts_cfg kcfg = *cfg;
+    kcfg.max_rollout_moves = 1;  // (unused: no rollout)
+    kcfg.rollout_policy = BK_MCTS_ROLLOUT_RANDOM;
+    L.a = MctsArgs{c.s_roots.dev(), c.s_sets.dev(), c.s_players.dev(), c.d_hash, n_games, kcfg, c.s_zob.dev(),
+                   c.s_zidx.dev(), nullptr, c.s_ttk.dev(), c.s_ttv.dev(), c.s_ttn.dev(), c.s_log.dev(), c.log_len,
+                   c.d_nodes, c.s_rewards.dev(), c.s_hits.dev(), c.s_out.dev(), nullptr, nullptr,
+                   h->d_counter, steps, c.time_ticks, MC_TREE_BATCH, 1, 1, 1};
+    L.a.state_rows = 0;
+    L.a.done = nullptr;
+    if ((rc = c.arm(L.a))) return rc;
+    L.a.kernel_id = kernel_id;
+    L.blocks = blocks;
+    L.prior = s_prior.dev();
+    L.bias = s_bias.dev();
+    return BK_OK;
+}
+
 int bk_mcts_learned(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const uint8_t* players,
                     const uint64_t* root_hash, int32_t n_games, const bk_mcts_cfg* cfg, const uint64_t* zobrist,
                     int32_t n_zobrist, const int32_t* zobrist_index, uint64_t* tt_keys, double* tt_vals,
@@ -8702,41 +8882,42 @@ int bk_mcts_learned(bk_handle h, const bk_state* roots, const bk_fset* root_sets
     if (rc) return rc;
     if (max_turns < 0) return set_err(h, BK_EINVAL, "bk_mcts_learned: max_turns must be >= 0%s", "");
     if (n_games == 0) return BK_OK;
-    rc = c.check_buffers(!bias_updates || (bias_weight != 0.0 && !prior_bias), cfg->flags != 0,
-                         "bk_mcts_learned: bad cfg (iterations/node_cap/iter_stop/resume; flags must be 0)%s");
+    LearnedLaunch L{};
+    rc = learned_prepare(c, bias_weight, prior_bias, bias_updates, BK_DIAG_K_COOP_L,
+                         "bk_mcts_learned: bad cfg (iterations/node_cap/iter_stop/resume; flags must be 0)%s",
+                         "bk_mcts_learned: bad player / zobrist_index%s", L);
     if (rc) return rc;
-    rc = c.check_games([](int32_t) { return false; }, "bk_mcts_learned: bad player / zobrist_index%s");
-    if (rc) return rc;
-    if ((rc = c.stage())) return rc;
-    const size_t n = (size_t)n_games;
-    const auto s_prior = c.st.add(bias_weight != 0.0 ? prior_bias : nullptr, sizeof(double) * (size_t)cfg->node_cap * n, c.io);
-    const auto s_bias = c.st.add(bias_updates, sizeof(int32_t) * n, c.io);
-    if ((rc = c.commit())) return rc;
-    // persistent grid of COOP_WAVES-search blocks; the search's McLane and slab live in LDS
-    // (DESIGN.md 4 has the kernel's resources)
-    int coop_bpc = 3;  // by LDS: 48 KB per block
-    if (tune_or(h, BK_TUNE_COOP_BLOCKS_PER_CU, 0) > 0) coop_bpc = (int)h->tune[BK_TUNE_COOP_BLOCKS_PER_CU];
-    int blocks = h->num_cu * coop_bpc;
-    const int need = (int)(((int64_t)n_games + COOP_WAVES - 1) / COOP_WAVES);
-    if (blocks > need) blocks = need;
-    if (blocks < 1) blocks = 1;
-    const uint32_t nslots = (uint32_t)blocks * COOP_WAVES;
-    const uint64_t per_wave = ((uint64_t)n_games + nslots - 1) / nslots + 1;
-    const uint64_t steps = 2 * per_wave * ((uint64_t)cfg->iterations + 1) * 3 + 64;  // one movegen per iteration
-    bk_mcts_cfg kcfg = *cfg;
-    kcfg.max_rollout_moves = 1;  // (unused: no rollout)
-    kcfg.rollout_policy = BK_MCTS_ROLLOUT_RANDOM;
-    MctsArgs a{c.s_roots.dev(), c.s_sets.dev(), c.s_players.dev(), c.d_hash, n_games, kcfg, c.s_zob.dev(),
-               c.s_zidx.dev(), nullptr, c.s_ttk.dev(), c.s_ttv.dev(), c.s_ttn.dev(), c.s_log.dev(), log_len,
-               c.d_nodes, c.s_rewards.dev(), c.s_hits.dev(), c.s_out.dev(), nullptr, nullptr,
-               h->d_counter, steps, c.time_ticks, MC_TREE_BATCH, 1, 1, 1};
-    a.state_rows = 0;
-    a.done = nullptr;
-    if ((rc = c.arm(a))) return rc;
-    a.kernel_id = BK_DIAG_K_COOP_L;
-    LeafArgs la{*model, max_turns, bias_weight, s_prior.dev(), s_bias.dev()};
-    BK_LAUNCH(h, k_mcts_coop_l, dim3(blocks), dim3(COOP_WAVES * WAVE), a, la);
+    LeafArgs la{*model, max_turns, bias_weight, L.prior, L.bias};
+    BK_LAUNCH(h, k_mcts_coop_l, dim3(L.blocks), dim3(COOP_WAVES * WAVE), L.a, la);
     return c.finish("bk_mcts_learned: step guard tripped%s");
+}
+
+int bk_mcts_learned_gbt(bk_handle h, const bk_state* roots, const bk_fset* root_sets, const uint8_t* players,
+                        const uint64_t* root_hash, int32_t n_games, const bk_mcts_cfg* cfg, const uint64_t* zobrist,
+                        int32_t n_zobrist, const int32_t* zobrist_index, uint64_t* tt_keys, double* tt_vals,
+                        int32_t* tt_count, const double* log_table, int32_t log_len, int32_t model_id,
+                        int32_t max_turns, double bias_weight, double* prior_bias, int32_t* bias_updates,
+                        bk_mcts_node* nodes, double* rewards, uint8_t* hit_flags, bk_mcts_out* out, int mem) {
+    MctsCall c{h, "bk_mcts_learned_gbt", roots, root_sets, players, root_hash, n_games, cfg, zobrist, n_zobrist,
+               zobrist_index, tt_keys, tt_vals, tt_count, log_table, log_len, nodes, rewards, hit_flags, out, mem};
+    if (c.bad_args()) return set_err(h, BK_EINVAL, "bk_mcts_learned_gbt: invalid arguments%s", "");
+    // the model, the weight and max_turns are judged before anything else, an empty batch included
+    const bk_handle_s::GbtSlot* g = gbt_slot(h, model_id);
+    if (!g) return set_err(h, BK_EINVAL, "bk_mcts_learned_gbt: unknown or freed model_id%s", "");
+    if (!__builtin_isfinite(bias_weight))
+        return set_err(h, BK_EINVAL, "bk_mcts_learned_gbt: the bias weight is not finite%s", "");
+    if (max_turns < 0) return set_err(h, BK_EINVAL, "bk_mcts_learned_gbt: max_turns must be >= 0%s", "");
+    if (n_games == 0) return BK_OK;
+    LearnedLaunch L{};
+    const int rc = learned_prepare(c, bias_weight, prior_bias, bias_updates, BK_DIAG_K_COOP_G,
+                                   "bk_mcts_learned_gbt: bad cfg (iterations/node_cap/iter_stop/resume; flags must be 0)%s",
+                                   "bk_mcts_learned_gbt: bad player / zobrist_index%s", L);
+    if (rc) return rc;
+    const char* base = (const char*)g->d;
+    GbtLeafArgs ga{(const bk_gbt_model*)base, (const int32_t*)(base + g->roots_off), (const GbtNode*)(base + g->nodes_off),
+                   max_turns, bias_weight, L.prior, L.bias};
+    BK_LAUNCH(h, k_mcts_coop_g, dim3(L.blocks), dim3(COOP_WAVES * WAVE), L.a, ga);
+    return c.finish("bk_mcts_learned_gbt: step guard tripped%s");
 }
 
 }  // extern "C"

@@ -744,13 +744,18 @@ class BlokusGPU:
         """bk_mcts_learned with every buffer a torch CUDA tensor on this device (BK_MEM_DEVICE,
         torch's current stream): mcts_device's searches with learned leaf evaluation in place
         of the rollouts (k_mcts_coop_l), so there is no mt_state.  model: a WinProbModel (or a
-        BkWinprobModel).  bias_weight != 0 turns progressive bias on and needs prior_bias
+        BkWinprobModel), or a GbtPhaseModel: that one goes to bk_mcts_learned_gbt (k_mcts_coop_g)
+        with the id of its resident copy (gbt_model_id), every other argument the same.
+        bias_weight != 0 turns progressive bias on and needs prior_bias
         float64[n, node_cap]; bias_updates int32[n] receives each search's update count.
         chunk > 0 splits the searches into launches of `chunk` iterations (same result).
         check=False leaves the status words in `out` to the caller instead of raising."""
         import torch
         n = roots.shape[0]
         native = model.as_native() if hasattr(model, "as_native") else model
+        gbt = isinstance(native, tuple)  # (bk_gbt_model, roots, nodes): searched by its resident id
+        entry, arg = ((self.handle.mcts_learned_gbt, self.gbt_model_id(model)) if gbt
+                      else (self.handle.mcts_learned, native))
         own = dict(bias_updates=(bias_updates, torch.int32, (n,)))
         if bias_weight != 0.0:
             if prior_bias is None:
@@ -764,13 +769,12 @@ class BlokusGPU:
         assert not (chunk and time_limit_us), "timed searches run in one launch"
         for _, cfg in _search_cfgs(mcts_chunks(iterations, chunk), False, iterations, 1, exploration, tt_keys,
                                    node_cap, time_limit_us, 0, 0):
-            self.handle.mcts_learned(d(roots), d(root_sets), d(players), d(root_hash), n, cfg, d(zobrist),
-                                     zobrist.shape[0], d(zobrist_index), d(tt_keys), d(tt_vals), d(tt_count),
-                                     d(log_table), log_table.shape[0], native, max_turns, bias_weight,
-                                     d(prior_bias) if bias_weight != 0.0 else 0, d(bias_updates), d(nodes),
-                                     d(rewards), d(hit_flags), d(out), N.MEM_DEVICE)
+            entry(d(roots), d(root_sets), d(players), d(root_hash), n, cfg, d(zobrist), zobrist.shape[0],
+                  d(zobrist_index), d(tt_keys), d(tt_vals), d(tt_count), d(log_table), log_table.shape[0], arg,
+                  max_turns, bias_weight, d(prior_bias) if bias_weight != 0.0 else 0, d(bias_updates), d(nodes),
+                  d(rewards), d(hit_flags), d(out), N.MEM_DEVICE)
         if check:
-            _raise_stopped_early("bk_mcts_learned", out)
+            _raise_stopped_early("bk_mcts_learned_gbt" if gbt else "bk_mcts_learned", out)
 
     def _check_search_tensors(self, n, iterations, tt_rows, roots, root_sets, players, root_hash, zobrist,
                               zobrist_index, log_table, nodes, out, tt_keys, tt_vals, tt_count, rewards, hit_flags,

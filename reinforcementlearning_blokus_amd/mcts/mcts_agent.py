@@ -41,6 +41,12 @@ searches of ``search`` and ``kernel`` do not evaluate leaves and reject these op
   ``dummy_model.json`` evaluator, and progressive bias with a weight of 0 (the kernel reads
   weight 0 as bias off, the host tree would still count its updates): each raises a
   ``ValueError`` that names ``exact``.
+* ``rollout_backend="leaf_gbt"`` (opt-in): ``leaf`` for a ``pairwise_gbt_phase`` model, the
+  whole search in one bk_mcts_learned_gbt launch (k_mcts_coop_g walks the model's trees in
+  the search's own wave; every value is bit for bit what bk_winprob_eval_gbt returns).  It
+  takes exactly the options ``leaf`` takes and refuses what ``leaf`` refuses; a logistic
+  model is sent to ``leaf``, and ``leaf`` keeps refusing tree models.  ``search_batch`` takes
+  such agents too: one launch per tree model, never one shared with logistic agents.
 """
 from __future__ import annotations
 
@@ -307,6 +313,10 @@ TIMED_MAX_ITERS_PER_S = 20000
 TIMED_MAX_ITERS = 1 << 18
 
 
+# the in-kernel learned backends and the model kind each one's kernel evaluates
+_LEAF_MODEL = {"leaf": "pairwise_logreg", "leaf_gbt": "pairwise_gbt_phase"}
+
+
 class MCTSNode:
     def __init__(self, board: Board, player: Player, move: Optional[Move] = None,
                  parent: Optional["MCTSNode"] = None):
@@ -381,17 +391,18 @@ class MCTSAgent:
             raise ValueError("learned_model_path is required when learned evaluation, progressive bias, "
                              "or potential shaping is enabled.")
         learned = bool(self._requires_learned_evaluator or self.learned_model_path)
-        if rollout_backend == "leaf":
+        if rollout_backend in _LEAF_MODEL:  # "leaf" and "leaf_gbt" take the same options
+            name = f"rollout_backend='{rollout_backend}'"
             if self.potential_shaping_enabled:
-                raise ValueError("rollout_backend='leaf': potential shaping needs rollouts; use rollout_backend='exact'")
+                raise ValueError(f"{name}: potential shaping needs rollouts; use rollout_backend='exact'")
             if self.progressive_bias_enabled and not self.leaf_evaluation_enabled:
-                raise ValueError("rollout_backend='leaf' runs progressive bias only together with leaf evaluation; "
+                raise ValueError(f"{name} runs progressive bias only together with leaf evaluation; "
                                  "use rollout_backend='exact'")
             if not self.leaf_evaluation_enabled:
-                raise ValueError("rollout_backend='leaf' needs leaf_evaluation_enabled=True and a learned_model_path; "
+                raise ValueError(f"{name} needs leaf_evaluation_enabled=True and a learned_model_path; "
                                  "without leaf evaluation use rollout_backend='search' or 'exact'")
             if self.progressive_bias_enabled and float(progressive_bias_weight) == 0.0:
-                raise ValueError("rollout_backend='leaf': a progressive_bias_weight of 0 turns the bias off in the "
+                raise ValueError(f"{name}: a progressive_bias_weight of 0 turns the bias off in the "
                                  "kernel; use rollout_backend='exact'")
         if learned and rollout_backend in ("search", "kernel"):
             raise ValueError(f"rollout_backend='{rollout_backend}': the in-kernel search does not evaluate leaves; "
@@ -415,8 +426,8 @@ class MCTSAgent:
         if rollout_backend is None:
             rollout_backend = "search" if _search_policy(rollout_agent) is not None else "exact"
         self.rollout_backend = rollout_backend
-        if self.rollout_backend not in ("search", "exact", "kernel", "leaf"):
-            raise ValueError("rollout_backend must be 'search', 'exact', 'kernel' or 'leaf'")
+        if self.rollout_backend not in ("search", "exact", "kernel", "leaf", "leaf_gbt"):
+            raise ValueError("rollout_backend must be 'search', 'exact', 'kernel' or 'leaf' (or 'leaf_gbt')")
         if self.rollout_backend == "exact" and rollout_agent is None:
             raise ValueError("rollout_backend='exact' needs a rollout_agent")
         if self.rollout_backend == "search" and _search_policy(rollout_agent) is None:
@@ -435,13 +446,20 @@ class MCTSAgent:
                 self.learned_evaluator = LearnedWinProbabilityEvaluator(self.learned_model_path,
                                                                         potential_mode=potential_mode, device=device)
             except ValueError as e:
-                if self.rollout_backend != "leaf":
+                if self.rollout_backend not in _LEAF_MODEL:
                     raise
-                raise ValueError(f"rollout_backend='leaf' needs a pairwise_logreg model ({e}); other evaluators "
-                                 "belong to rollout_backend='exact'") from None
-            if self.rollout_backend == "leaf" and self.learned_evaluator.model_type != "pairwise_logreg":
-                raise ValueError(f"rollout_backend='leaf' needs a pairwise_logreg model, {self.learned_model_path} is "
-                                 f"a {self.learned_evaluator.model_type} evaluator; use rollout_backend='exact'")
+                raise ValueError(f"rollout_backend='{self.rollout_backend}' needs a {_LEAF_MODEL[self.rollout_backend]} "
+                                 f"model ({e}); other evaluators belong to rollout_backend='exact'") from None
+            have, want = self.learned_evaluator.model_type, _LEAF_MODEL.get(self.rollout_backend)
+            if want is not None and have != want:
+                # a model of the other in-kernel backend's kind is sent there, anything else to the host tree
+                msg = (f"rollout_backend='{self.rollout_backend}' needs a {want} model, {self.learned_model_path} is "
+                       f"a {have} evaluator; use rollout_backend=")
+                if self.rollout_backend == "leaf":
+                    msg += "'exact'" + (", or 'leaf_gbt' to search it in one launch" if have == _LEAF_MODEL["leaf_gbt"] else "")
+                else:
+                    msg += "'leaf'" if have == _LEAF_MODEL["leaf"] else "'exact'"
+                raise ValueError(msg)
         self.last_root_children: List[List[float]] = []  # "leaf": [move, visits, total, prior_bias] per root child
         self.stats = self._fresh_stats()
 
@@ -457,7 +475,7 @@ class MCTSAgent:
             return None
         if len(legal_moves) == 1:
             return legal_moves[0]
-        if self.rollout_backend in ("search", "leaf"):
+        if self.rollout_backend in ("search", "leaf", "leaf_gbt"):
             return MCTSAgent.search_batch([self], [board], [player], [legal_moves])[0]
         t0 = time.time()
         root = MCTSNode(board, player)
@@ -483,7 +501,8 @@ class MCTSAgent:
         """select_action for several "search"-backend agents in ONE bk_mcts launch (one
         search per agent; an agent appears at most once).  "leaf" agents may be among them:
         they go to bk_mcts_learned launches of their own (never in a group with "search"
-        agents).  Each result equals the agent's own select_action on that position: the
+        agents; "leaf_gbt" agents likewise, in bk_mcts_learned_gbt launches).  Each result
+        equals the agent's own select_action on that position: the
         search reads and advances the agent's rollout stream and TT, and updates its stats,
         exactly as the reference's select_action (mcts/mcts_agent.py:304-341) does.
         Positions with < 2 legal moves are answered without a search (:313-318);
@@ -515,8 +534,8 @@ class MCTSAgent:
         out: List[Optional[int]] = [None] * len(agents)
         groups = {}  # agents sharing (iterations, rollout cap, c, TT on/off, time limit) share a launch
         for i, a in enumerate(agents):
-            if a.rollout_backend not in ("search", "leaf"):
-                raise ValueError("search_batch needs rollout_backend='search' or 'leaf' agents")
+            if a.rollout_backend not in ("search", "leaf", "leaf_gbt"):
+                raise ValueError("search_batch needs rollout_backend='search' or 'leaf' agents (or 'leaf_gbt')")
             # time_limit (seconds, mcts_agent.py:325-333, :349-356): iterate until it runs
             # out, ignoring `iterations`, as _run_mcts_with_time_limit does.  The kernel stops
             # each search at the first iteration boundary past the limit; the launch still
@@ -528,11 +547,13 @@ class MCTSAgent:
             iters = int(a.iterations)
             if tl_us:
                 iters = int(min(TIMED_MAX_ITERS, max(16, math.ceil(float(a.time_limit) * TIMED_MAX_ITERS_PER_S))))
-            if a.rollout_backend == "leaf":  # one launch per (iterations, c, TT, time limit, model values, max_turns, bias)
+            if a.rollout_backend in _LEAF_MODEL:
+                # one launch per (backend, iterations, c, TT, time limit, model values, max_turns, bias): a
+                # tree model and a logistic model never share one
                 ev = a.learned_evaluator
                 bias_w = a.progressive_bias_weight if a.progressive_bias_enabled else 0.0
-                key = ("leaf", iters, float(a.exploration_constant), a.use_transposition_table, tl_us, ev.model.key(),
-                       int(ev.max_turns), float(bias_w))
+                key = (a.rollout_backend, iters, float(a.exploration_constant), a.use_transposition_table, tl_us,
+                       ev.model.key(), int(ev.max_turns), float(bias_w))
                 groups.setdefault(key, []).append(i)
                 continue
             policy = _search_policy(a.rollout_agent)
@@ -542,7 +563,7 @@ class MCTSAgent:
                    tl_us, policy)
             groups.setdefault(key, []).append(i)
         for key, idx in groups.items():
-            if key[0] == "leaf":
+            if key[0] in _LEAF_MODEL:
                 MCTSAgent._leaf_group(agents, roots, sets, players, key, idx, out)
                 continue
             iters, max_roll, c, use_tt, tl_us, policy = key
@@ -584,7 +605,8 @@ class MCTSAgent:
 
     @staticmethod
     def _leaf_group(agents, roots, sets, players, key, idx, out) -> None:
-        """search_packed's launch for one group of "leaf" agents; stats as the exact backend
+        """search_packed's launch for one group of "leaf" or "leaf_gbt" agents (the group's
+        model decides the entry point: gpu.mcts_learned_device); stats as the exact backend
         leaves them (leaf_eval_calls, progressive_bias_updates, the non-hit rewards)."""
         from ..gpu import BlokusGPU
         _, iters, c, use_tt, tl_us, _, max_turns, bias_w = key
