@@ -3314,8 +3314,83 @@ __device__ __forceinline__ void capture_checkpoint(const RolloutArgs& a, const C
     sn.turn[at] = (int32_t)(g.turns0 + (uint32_t)g.turns);
 }
 
-template <bool FR, bool HEUR = false, bool SNAP = false>
+// ---- k_rollout_fr, BK_SEM_ARENA: lanes without a game look ahead for stuck players ------
+// An iteration of rollout_body is wave-wide: a lane that has no game runs the stencil on
+// zero planes.  Such a lane (a helper) instead counts the moves of a player that is not to
+// move yet, on the board of a lane that has a game (a client) as it stands at the top of
+// the iteration.  No move there means no move on any later board of that game (placements
+// only take options away, and a player's frontier changes only when it places), so the
+// client notes the player as known stuck (Game::status bits 8..11, which no record keeps)
+// and, when that player's turn comes, passes it in the skip loop -- which sets the out bit
+// and bumps the counts exactly as the discovery iteration would have -- without spending a
+// wave iteration on it.  The game position at which g.out reaches 0xF, the out bits of a
+// capped game, the counts and the draws are those of the plain kernel.  A helper that finds
+// a move learns nothing (the board changes before that player moves) and writes nothing.
+//
+// Helper k (idle lanes in lane order) takes client k / 3 (lanes with a game in lane order)
+// and that client's (k % 3 + 1)-th player after the mover that is not known stuck.  The
+// hand-over goes through dwords of the wave's LDS area that the counts (CNT_DWORDS of the 40
+// per lane) leave free, so nothing of it is held in registers across the stencil:
+#define HELP_POST 31   // [client rank] the client's lane | mover << 8 | known stuck << 12 | first << 16
+#define HELP_USED 32   // .. 35 [client rank] the client's used-piece words, players 0..3
+#define HELP_PAIR 36   // [lane] the helper's client lane | player << 6 | 0x100 (0: no pair)
+#define HELP_FOUND 37  // [lane] the players this client's helpers found stuck
+static_assert(CNT_DWORDS <= HELP_POST && HELP_FOUND < ROLL_WORDS_FR / WAVE, "the hand-over dwords are free");
+
+__device__ __forceinline__ void wave_lds_sync() {  // the wave's LDS writes are visible to its lanes
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// clients: lanes with a game (uniform, neither empty nor full).  True for a helper with a
+// pair: the client's lane, the player to look at, its first-move bit and its free pieces
+__device__ __forceinline__ bool help_assign(uint32_t* my, int lane, uint64_t clients, const Game& g,
+                                            uint32_t& client_lane, int& q, uint32_t& first, uint32_t& avail) {
+    const bool idle = !((clients >> lane) & 1ull);
+    const uint32_t below = (uint32_t)__popcll(clients & ((1ull << lane) - 1ull));
+    const uint32_t rank = idle ? (uint32_t)lane - below : below;  // among the helpers / the clients
+    my[HELP_FOUND * WAVE + lane] = 0u;
+    my[HELP_PAIR * WAVE + lane] = 0u;
+    if (!idle) {
+        my[HELP_POST * WAVE + rank] = (uint32_t)lane | ((uint32_t)g.cur << 8) |
+                                      (((g.out | (g.status >> 8)) & 0xFu) << 12) | ((g.first & 0xFu) << 16);
+        my[(HELP_USED + 0) * WAVE + rank] = g.used.v0;
+        my[(HELP_USED + 1) * WAVE + rank] = g.used.v1;
+        my[(HELP_USED + 2) * WAVE + rank] = g.used.v2;
+        my[(HELP_USED + 3) * WAVE + rank] = g.used.v3;
+    }
+    wave_lds_sync();
+    const uint32_t c = rank / 3u, k = rank - 3u * c;
+    if (!idle || c >= (uint32_t)__popcll(clients)) return false;
+    const uint32_t post = my[HELP_POST * WAVE + c];
+    const uint32_t cur = (post >> 8) & 3u, open = ~(post >> 12) & 0xFu;
+    uint32_t r = ((open | (open << 4)) >> cur) & 0xEu;  // bit d: the player d seats after the mover
+    if (k >= 1u) r &= r - 1u;
+    if (k >= 2u) r &= r - 1u;
+    if (r == 0u) return false;
+    q = (int)((cur + (uint32_t)__builtin_ctz(r)) & 3u);
+    client_lane = post & (WAVE - 1);
+    first = (post >> (16 + q)) & 1u;
+    avail = ~my[(HELP_USED + q) * WAVE + c] & 0x1FFFFFu;
+    my[HELP_PAIR * WAVE + lane] = client_lane | ((uint32_t)q << 6) | 0x100u;
+    return true;
+}
+
+// after the counts: a helper whose player has no move tells its client
+__device__ __forceinline__ void help_report(uint32_t* my, int lane, bool idle, uint32_t total, Game& g) {
+    if (idle) {
+        const uint32_t pair = my[HELP_PAIR * WAVE + lane];
+        if (pair != 0u && total == 0u) atomicOr(&my[HELP_FOUND * WAVE + (pair & (WAVE - 1))], 1u << ((pair >> 6) & 3u));
+    }
+    wave_lds_sync();
+    if (!idle) g.status |= my[HELP_FOUND * WAVE + lane] << 8;
+}
+
+// HELP (k_rollout_fr): idle lanes look ahead for stuck players (BK_SEM_ARENA launches)
+template <bool FR, bool HEUR = false, bool SNAP = false, bool HELP = false>
 __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const CaptureArgs& sn = CaptureArgs{}) {
+    static_assert(!HELP || (FR && !HEUR && !SNAP), "the look-ahead is k_rollout_fr's");
     constexpr int BLK = HEUR ? HBLOCK : BLOCK;
     constexpr int AREA = HEUR ? HEUR_WORDS : FR ? ROLL_WORDS_FR : ROLL_WORDS_PER_WAVE;
     constexpr int HS_WORDS = HEUR ? (int)(sizeof(HeurShared) + 7) / 4 : 0;
@@ -3343,6 +3418,9 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Capture
     // k_rollout_fr carries each table's live-slot mask from ply to ply (live_masks): in the
     // slab words of the compat RNG when no RNG state lives there
     const bool lm_in_slab = FR && !HEUR && a.cfg.rng == BK_RNG_PHILOX && a.rng_io == nullptr;
+    // (ADVANCE's cap rule treats the player after the last mover specially, and SEM_ROLLOUT
+    // has no passes: neither takes the look-ahead)
+    const bool help = HELP && a.cfg.semantics == BK_SEM_ARENA;
 
     Game g;
     g.pid = -1;
@@ -3383,9 +3461,12 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Capture
                 // (ADVANCE: once the placement budget is used nobody passes any more -- the
                 // player after the last mover is left to move, stuck or not:
                 // generate_random_valid_state leaves its loop before it looks at that player)
+                // (HELP: a player that a helper found stuck passes here at its turn, which
+                // sets its out bit where the discovery iteration would have)
 #pragma unroll 1
-                for (int s = 0; s < 4 && ((g.out >> g.cur) & 1u) && g.out != 0xFu &&
+                for (int s = 0; s < 4 && (((HELP ? g.out | (g.status >> 8) : g.out) >> g.cur) & 1u) && g.out != 0xFu &&
                                 (advance ? g.plies : g.turns) < g.cap; ++s) {
+                    if constexpr (HELP) g.out |= 1u << g.cur;
                     g.passes++; g.turns++; g.since_move++;
                     g.cur = (g.cur + 1) & 3;
                 }
@@ -3404,22 +3485,35 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Capture
             if (lane == 0) { atomicOr(&a.counter[1], 1u); atomicOr(&a.counter[2], BK_STICKY_GUARD); }
             break;
         }
+        const bool idle = done || g.pid < 0;
+        // HELP: an idle lane may take a player of a client's board instead of zero planes
+        bool helping = false;
+        uint32_t h_lane = 0, h_first = 0, h_avail = 0;
+        int h_q = 0;
+        if constexpr (HELP) {
+            const uint64_t clients = __ballot(!idle);
+            if (help && clients != ~0ull)  // (clients != 0: a lane is not done)
+                helping = help_assign(my, lane, clients, g, h_lane, h_q, h_first, h_avail);
+        }
         SECT(1);
         // ---- derive + movegen for every active lane (uniform work)
-        const bool idle = done || g.pid < 0;
-        const int p = idle ? 0 : g.cur;
+        const int p = HELP && helping ? h_q : idle ? 0 : g.cur;
         Planes P;
         {
+            // (a helper reads its client's rows: same wave, so the slot is this lane's plus
+            // the lane distance; before the client's apply stores of this iteration)
+            const Slab src{HELP && helping ? a.slab + (size_t)(slot - (uint32_t)lane + h_lane) * SLAB_WORDS : slab.base};
+            const bool blank = HELP ? idle && !helping : idle;
             uint32_t own[20], occ[20];
 #pragma unroll
             for (int R = 0; R < 20; ++R) {
-                own[R] = idle ? 0u : slab.at(p, R);
-                occ[R] = idle ? 0u : slab.at(4, R);
+                own[R] = blank ? 0u : src.at(p, R);
+                occ[R] = blank ? 0u : src.at(4, R);
             }
-            derive_rows(own, occ, (g.first >> p) & 1u, p, P);
+            derive_rows(own, occ, HELP && helping ? h_first : (g.first >> p) & 1u, p, P);
         }
         make_pairs(P);
-        const uint32_t avail = idle ? 0u : (~g.used.get(p) & 0x1FFFFFu);
+        const uint32_t avail = HELP && helping ? h_avail : idle ? 0u : (~g.used.get(p) & 0x1FFFFFu);
         uint32_t total;
         int gs = 0;
         uint32_t kk = 0;
@@ -3469,6 +3563,9 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Capture
             total = movegen_counts<true>(P, avail, my, lane);
         }
         SECT(2);
+        if constexpr (HELP) {  // (the pairs were dealt this iteration iff the wave has an idle lane)
+            if (help && __ballot(idle) != 0ull) help_report(my, lane, idle, total, g);
+        }
         if (idle) continue;
         if (FR && total > 0u && ((g.smask >> p) & 1u) && !forced) {  // a search seat is to move: hand the game back
             if constexpr (HEUR) {
@@ -3644,7 +3741,9 @@ __global__ void k_advance(RolloutArgs a);
 #endif
 // reference frontier order (compat parity mode)
 #if BK_DEF(BK_U_ROLLOUT_FR)
-__global__ __launch_bounds__(BLOCK, FR_BLOCKS_PER_CU) void k_rollout_fr(RolloutArgs a) { rollout_body<true>(a); }
+__global__ __launch_bounds__(BLOCK, FR_BLOCKS_PER_CU) void k_rollout_fr(RolloutArgs a) {
+    rollout_body<true, false, false, true>(a);
+}
 #else
 __global__ void k_rollout_fr(RolloutArgs a);
 #endif
