@@ -461,7 +461,13 @@ int bk_debug_fastmcts_select(bk_handle h, int32_t n, const uint32_t* visits, con
  * rewards / hit_flags (optional, [g * cfg.iterations + i]): per iteration the simulated
  * reward and 1 if it came from the TT (stats["rollout_rewards"] = the non-hit ones).
  * out[g].status != 0 means the search stopped early (see BK_MCTS_E*): enlarge the pool /
- * TT and retry from the saved inputs.
+ * TT and retry from the saved inputs.  BK_MCTS_ETT: a table never holds more than
+ * tt_cap - 1 entries (one slot stays empty so that every probe ends).  The search whose
+ * rollout's insert would fill the last slot keeps its table as it was (tt_count ==
+ * tt_cap - 1, no slot written), still records that rollout's reward and backpropagates
+ * it, and stops there: with the insert refused at iteration k (0-based), iterations_run
+ * == k + 1 and rewards / hit_flags [0, k) are those of a search with a larger table.
+ * The other searches of the launch are not affected.
  */
 #define BK_MCTS_NODE_EVALUATED 1u
 typedef struct bk_mcts_node {

@@ -1029,12 +1029,14 @@ static double or_rollout_mt(const or_board* b, int player, or_mt* rng, int max_m
     return r;
 }
 
-int or_mcts(const or_board* board, int player, int iterations, double c, int max_rollout,
-            const double* log_table, int log_len, const uint64_t* ztab, or_mt* rng, int use_tt,
-            uint64_t* tt_keys, double* tt_vals, int tt_cap, int32_t* tt_count,
-            int32_t* best_move, int32_t* hits, double* rewards, uint8_t* hit_flags,
-            int32_t* child_moves, int32_t* child_visits, double* child_totals, int child_cap,
-            int32_t* n_children) {
+/* the search of or_mcts and or_mcts_tree; tree_* may be null (or_mcts) */
+static int mcts_run(const or_board* board, int player, int iterations, double c, int max_rollout,
+                    const double* log_table, int log_len, const uint64_t* ztab, or_mt* rng, int use_tt,
+                    uint64_t* tt_keys, double* tt_vals, int tt_cap, int32_t* tt_count,
+                    int32_t* best_move, int32_t* hits, double* rewards, uint8_t* hit_flags,
+                    int32_t* child_moves, int32_t* child_visits, double* child_totals, int child_cap,
+                    int32_t* n_children, int32_t* tree_i32, double* tree_total, int tree_cap,
+                    int32_t* n_nodes, int32_t* iterations_done) {
     int32_t* scratch = (int32_t*)malloc(sizeof(int32_t) * BK_ORIENTS * 400);
     or_mnode* nodes = (or_mnode*)malloc(sizeof(or_mnode) * (size_t)(iterations + 1));
     int nn = 0, rc = 0;
@@ -1053,8 +1055,8 @@ int or_mcts(const or_board* board, int player, int iterations, double c, int max
         ++nn;                                                                          \
     } while (0)
     NEW_NODE(board, player, -1, -1);
-    int nhits = 0;
-    for (int it = 0; it < iterations; ++it) {
+    int nhits = 0, it = 0;
+    for (; it < iterations; ++it) {
         int u = 0;
         /* _selection */
         while (!(nodes[u].n_untried == 0 && nodes[u].nchild == 0)) {
@@ -1135,10 +1137,41 @@ int or_mcts(const or_board* board, int player, int iterations, double c, int max
         *hits = nhits;
     }
 done:
+    if (iterations_done) *iterations_done = it;
+    if (n_nodes) *n_nodes = nn;
+    for (int i = 0; i < nn && i < tree_cap && tree_i32; ++i) {
+        const or_mnode* z = &nodes[i];
+        int32_t* t = tree_i32 + 5 * i;
+        t[0] = z->parent; t[1] = z->move; t[2] = z->visits; t[3] = z->nchild; t[4] = z->n_untried + z->nchild;
+        tree_total[i] = z->total;
+    }
     for (int i = 0; i < nn; ++i) { free(nodes[i].untried); free(ch[i]); }
     free(ch); free(nodes); free(scratch);
     return rc;
 #undef NEW_NODE
+}
+
+int or_mcts(const or_board* board, int player, int iterations, double c, int max_rollout,
+            const double* log_table, int log_len, const uint64_t* ztab, or_mt* rng, int use_tt,
+            uint64_t* tt_keys, double* tt_vals, int tt_cap, int32_t* tt_count,
+            int32_t* best_move, int32_t* hits, double* rewards, uint8_t* hit_flags,
+            int32_t* child_moves, int32_t* child_visits, double* child_totals, int child_cap,
+            int32_t* n_children) {
+    return mcts_run(board, player, iterations, c, max_rollout, log_table, log_len, ztab, rng, use_tt, tt_keys,
+                    tt_vals, tt_cap, tt_count, best_move, hits, rewards, hit_flags, child_moves, child_visits,
+                    child_totals, child_cap, n_children, NULL, NULL, 0, NULL, NULL);
+}
+
+int or_mcts_tree(const or_board* board, int player, int iterations, double c, int max_rollout,
+                 const double* log_table, int log_len, const uint64_t* ztab, or_mt* rng, int use_tt,
+                 uint64_t* tt_keys, double* tt_vals, int tt_cap, int32_t* tt_count,
+                 int32_t* best_move, int32_t* hits, double* rewards, uint8_t* hit_flags,
+                 int32_t* child_moves, int32_t* child_visits, double* child_totals, int child_cap,
+                 int32_t* n_children, int32_t* tree_i32, double* tree_total, int tree_cap,
+                 int32_t* n_nodes, int32_t* iterations_done) {
+    return mcts_run(board, player, iterations, c, max_rollout, log_table, log_len, ztab, rng, use_tt, tt_keys,
+                    tt_vals, tt_cap, tt_count, best_move, hits, rewards, hit_flags, child_moves, child_visits,
+                    child_totals, child_cap, n_children, tree_i32, tree_total, tree_cap, n_nodes, iterations_done);
 }
 
 /* ---------------------------------------------------------------------------------

@@ -118,6 +118,8 @@ def lib():
                                   P(C.c_int32), P(C.c_int32), P(C.c_int32), C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, P(C.c_int32)]),
         }
+        sig["or_mcts_tree"] = (C.c_int, sig["or_mcts"][1] + [C.c_void_p, C.c_void_p, C.c_int, P(C.c_int32),
+                                                             P(C.c_int32)])
         for name, (res, args) in sig.items():
             f = getattr(L, name)
             f.restype = res
@@ -344,25 +346,28 @@ class TT:
         self.count = 0
 
 
-def mcts(b, player, iterations, exploration, max_rollout, ztab, rng, tt=None, child_cap=4096, heuristic=False):
-    """or_mcts: one MCTSAgent search (mcts/mcts_agent.py:304-582) with RandomAgent
-    rollouts (heuristic=True: HeuristicAgent rollouts, the reference's default) drawing
-    from `rng` (an MT, advanced in place).  tt: a TT or None."""
+def _grow(tt, iterations):
+    """Keep tt at most half full after `iterations` more inserts: re-insert the live keys
+    into a table twice as large, as often as needed."""
+    while (tt.count + iterations + 1) * 2 > len(tt.keys):
+        live = ~np.isnan(tt.vals)
+        k, v = tt.keys[live], tt.vals[live]
+        cap = len(tt.keys) * 2
+        tt.keys = np.zeros(cap, np.uint64)
+        tt.vals = np.full(cap, np.nan)
+        for kk, vv in zip(k.tolist(), v.tolist()):
+            i = kk & (cap - 1)
+            while not np.isnan(tt.vals[i]):
+                i = (i + 1) & (cap - 1)
+            tt.keys[i], tt.vals[i] = kk, vv
+
+
+def _search(b, player, iterations, exploration, max_rollout, ztab, rng, tt, child_cap, heuristic, tree):
+    """One call of or_mcts (tree False) or or_mcts_tree on tt's arrays as they are."""
     log_table = np.zeros(iterations + 2)
     log_table[1:] = np.log(np.arange(1, iterations + 2))
     use_tt = tt is not None
     if use_tt:
-        while (tt.count + iterations + 1) * 2 > len(tt.keys):  # grow: re-insert live keys
-            live = ~np.isnan(tt.vals)
-            k, v = tt.keys[live], tt.vals[live]
-            cap = len(tt.keys) * 2
-            tt.keys = np.zeros(cap, np.uint64)
-            tt.vals = np.full(cap, np.nan)
-            for kk, vv in zip(k.tolist(), v.tolist()):
-                i = kk & (cap - 1)
-                while not np.isnan(tt.vals[i]):
-                    i = (i + 1) & (cap - 1)
-                tt.keys[i], tt.vals[i] = kk, vv
         keys, vals, cap = tt.keys, tt.vals, len(tt.keys)
     else:
         keys, vals, cap = np.zeros(1, np.uint64), np.full(1, np.nan), 1
@@ -373,20 +378,56 @@ def mcts(b, player, iterations, exploration, max_rollout, ztab, rng, tt=None, ch
     cm = np.zeros(child_cap, np.int32)
     cv = np.zeros(child_cap, np.int32)
     ct = np.zeros(child_cap)
-    lib().or_set_rollout_policy(1 if heuristic else 0)
-    rc = lib().or_mcts(C.byref(b), player, iterations, exploration, max_rollout, log_table.ctypes.data,
-                       len(log_table), ztab.ctypes.data, C.byref(rng), int(use_tt), keys.ctypes.data,
-                       vals.ctypes.data, cap, C.byref(cnt), C.byref(best), C.byref(hits),
-                       rewards.ctypes.data, flags.ctypes.data, cm.ctypes.data, cv.ctypes.data,
-                       ct.ctypes.data, child_cap, C.byref(nch))
+    args = [C.byref(b), player, iterations, exploration, max_rollout, log_table.ctypes.data,
+            len(log_table), ztab.ctypes.data, C.byref(rng), int(use_tt), keys.ctypes.data,
+            vals.ctypes.data, cap, C.byref(cnt), C.byref(best), C.byref(hits),
+            rewards.ctypes.data, flags.ctypes.data, cm.ctypes.data, cv.ctypes.data,
+            ct.ctypes.data, child_cap, C.byref(nch)]
+    lib().or_set_rollout_policy(1 if heuristic else 0)  # this thread's policy
+    if tree:
+        ti = np.zeros((iterations + 1, 5), np.int32)
+        tot = np.zeros(iterations + 1)
+        nn, done = C.c_int32(), C.c_int32()
+        rc = lib().or_mcts_tree(*args, ti.ctypes.data, tot.ctypes.data, iterations + 1, C.byref(nn), C.byref(done))
+    else:
+        rc = lib().or_mcts(*args)
     lib().or_set_rollout_policy(0)
-    if rc != 0:
-        raise RuntimeError(f"or_mcts failed: {rc}")
     if use_tt:
         tt.count = cnt.value
     n = min(nch.value, child_cap)
-    return {"move": best.value, "hits": hits.value, "rewards": rewards, "hit_flags": flags,
-            "children": list(zip(cm[:n].tolist(), cv[:n].tolist(), ct[:n].tolist()))}
+    res = {"move": best.value, "hits": hits.value, "rewards": rewards, "hit_flags": flags,
+           "children": list(zip(cm[:n].tolist(), cv[:n].tolist(), ct[:n].tolist()))}
+    if tree:
+        k = nn.value
+        res.update(rc=rc, iterations_done=done.value, parent=ti[:k, 0].copy(), node_move=ti[:k, 1].copy(),
+                   visits=ti[:k, 2].copy(), n_children=ti[:k, 3].copy(), n_legal=ti[:k, 4].copy(), total=tot[:k].copy())
+    return rc, res
+
+
+def mcts(b, player, iterations, exploration, max_rollout, ztab, rng, tt=None, child_cap=4096, heuristic=False):
+    """or_mcts: one MCTSAgent search (mcts/mcts_agent.py:304-582) with RandomAgent
+    rollouts (heuristic=True: HeuristicAgent rollouts, the reference's default) drawing
+    from `rng` (an MT, advanced in place).  tt: a TT or None; it is grown first so that it
+    stays at most half full."""
+    if tt is not None:
+        _grow(tt, iterations)
+    rc, res = _search(b, player, iterations, exploration, max_rollout, ztab, rng, tt, child_cap, heuristic, False)
+    if rc != 0:
+        raise RuntimeError(f"or_mcts failed: {rc}")
+    return res
+
+
+def mcts_tree(b, player, iterations, exploration, max_rollout, ztab, rng, tt=None, child_cap=4096, heuristic=False,
+              grow=False):
+    """or_mcts_tree: mcts()'s search plus the whole tree in creation order (node 0 = root):
+    parent, node_move, visits, total, n_children, n_legal arrays, and rc / iterations_done.
+    tt is used at the capacity it has and never grown (grow=True: as mcts() grows it), so a
+    small table wraps, chains and may refuse an insert: rc == -3, never raised here, with
+    the table, tt.count and rewards[:iterations_done] as they were at the refusal (move,
+    hits and children are then unset)."""
+    if tt is not None and grow:
+        _grow(tt, iterations)
+    return _search(b, player, iterations, exploration, max_rollout, ztab, rng, tt, child_cap, heuristic, True)[1]
 
 
 # ---------------------------------------------------------------------------------
