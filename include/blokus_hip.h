@@ -117,7 +117,11 @@ typedef struct bk_result {
                                    is not certified equal to the reference's);             
                                    bit3: ARENA run stopped by the max_plies turn cap before
                                    every player was known to be stuck (passes / turns are
-                                   then raw and reserved[0] = passes since the last move)  */
+                                   then raw and reserved[0] = passes since the last move);
+                                   bit5 BK_STATUS_STOP, bit6: bk_arena_step's forced move is
+                                   not legal; bit7 BK_STATUS_BADSET: a heuristic seat names a
+                                   weight set its bk_heur_plan does not have (device path:
+                                   the game was not played)                                */
     uint16_t plies;             /* moves placed during the playout                          */
     uint16_t passes;            /* arena passes (arena_runner.py:660-664)                   */
     uint16_t turns;             /* arena turn_count                                         */
@@ -148,7 +152,8 @@ int bk_stream_create(bk_handle h, const uint32_t* cu_mask, int32_t mask_words, v
    kernel ends, so their input errors and guard trips surface here: BK_EOVERFLOW if a
    persistent kernel's iteration guard tripped (results incomplete), BK_EINVAL if a
    root_index entry was outside [0, n_roots) (that playout ran from root 0 with status
-   bit 2); both cleared once reported.  BK_ECHECK: a bk_mcts search broke a tree invariant
+   bit 2) or a heuristic seat named a weight set >= its plan's n_sets (that game was not
+   played: status BK_STATUS_BADSET); all cleared once reported.  BK_ECHECK: a bk_mcts search broke a tree invariant
    (bk_debug_mcts_failure has the record). */
 int bk_synchronize(bk_handle h);
 int bk_last_error(bk_handle h, char* buf, size_t len);
@@ -361,6 +366,41 @@ int bk_arena_step_snap(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, 
                        uint32_t* rng_state, bk_result* out, bk_stop_info* stop_out, const bk_snap_plan* plan,
                        int mem);
 int bk_snap_plan_size(void);
+
+/*
+ * HeuristicAgent seats with weights of their own (the arena's
+ * HeuristicAgent(seed).set_weights(params["weights"])): bk_rollout_frontier and
+ * bk_arena_step with a plan.  Which seats play the heuristic still comes from
+ * cfg->heuristic_seats / seat_masks; the plan says which of up to BK_HEUR_MAX_SETS weight
+ * sets each of them scores with (a set index on any other seat is ignored).  plan == NULL
+ * is the unsuffixed call and its kernel; with a plan the heuristic seats are played by
+ * k_rollout_fr_hw, with every rule of the base entry point unchanged.  The plan is copied
+ * at the call.  BK_EINVAL for n_sets outside 1..BK_HEUR_MAX_SETS, a non-finite weight, a
+ * set whose S = 5 |piece_size| + 20 |corner_creation| + 5 |edge_avoidance| +
+ * |center_preference| exceeds BK_HEUR_MAX_S (up to there every certified draw is the
+ * reference's), and, in host memory, a heuristic seat that names a set >=
+ * n_sets.  In device memory such a game is not played: nothing of it is read or written
+ * but out[i], which is zero except status BK_STATUS_BADSET, and bk_synchronize reports
+ * BK_EINVAL once; the other games of the launch are played as usual.
+ */
+#define BK_HEUR_MAX_SETS 4
+#define BK_HEUR_MAX_S 128.0
+#define BK_STATUS_BADSET 128         /* bk_result.status bit 7 */
+typedef struct bk_heur_plan {        /* POD, passed by pointer, copied at the call */
+    double  w[BK_HEUR_MAX_SETS][4];  /* piece_size, corner_creation, edge_avoidance, center_preference */
+    int32_t n_sets;                  /* 1..BK_HEUR_MAX_SETS */
+    uint8_t seat_sets_all;           /* bits 2p..2p+1: set of seat p, used when seat_sets is NULL */
+    const uint8_t* seat_sets;        /* [n] one byte per game, same packing; host or device per `mem`; may be NULL */
+} bk_heur_plan;
+int bk_heur_plan_size(void);
+int bk_rollout_frontier_w(bk_handle h, const bk_state* roots, const bk_fset* root_sets, int32_t n_roots,
+                          const int32_t* root_index, int32_t n_playouts, const bk_rollout_cfg* cfg,
+                          const uint32_t* compat_seeds, bk_result* out, bk_state* out_states,
+                          bk_fset* out_sets, const bk_heur_plan* plan, int mem);
+int bk_arena_step_w(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const bk_rollout_cfg* cfg,
+                    const uint8_t* seat_masks, const uint8_t* quick_masks, const int32_t* forced,
+                    uint32_t* rng_state, bk_result* out, bk_stop_info* stop_out, const bk_heur_plan* plan,
+                    int mem);
 
 /* numpy RandomState(seed) cursor for rng_state (host, no GPU) */
 int bk_mt_cursor_init(uint32_t seed, uint32_t* out4);

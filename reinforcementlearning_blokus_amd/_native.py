@@ -18,6 +18,11 @@ LIB_PATH = os.environ.get("BK_LIB_PATH") or os.path.join(_HERE, "_lib", "libblok
 
 OK, EINVAL, EHIP, ENOMEM, EOVERFLOW, ECHECK = 0, -1, -2, -3, -4, -5
 STATUS_CAP, STATUS_UNCERT, STATUS_STOP, STATUS_BADFORCE = 8, 16, 32, 64  # bk_result.status bits
+STATUS_BADSET = 128  # bk_result.status: a heuristic seat names a weight set the plan does not have (device memory)
+HEUR_MAX_SETS = 4  # BK_HEUR_MAX_SETS: weight sets of one bk_heur_plan
+HEUR_MAX_S = 128.0  # BK_HEUR_MAX_S: the largest S = 5|size| + 20|corner| + 5|edge| + |centre| of a set
+HEUR_WEIGHT_KEYS = ("piece_size", "corner_creation", "edge_avoidance", "center_preference")
+HEUR_DEFAULT_WEIGHTS = (1.0, 2.0, -1.5, 0.5)
 FORCE_INDEX = 0x40000000  # bk_arena_step forced[i]: the k-th entry of the legal list (BK_FORCE_INDEX | k)
 FORCE_SKIP = -2  # bk_arena_step forced[i]: leave game i untouched (its search is in flight)
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -45,6 +50,7 @@ EXPORTS = (
     "bk_gbt_node_size", "bk_gbt_model_size", "bk_gbt_model_check", "bk_gbt_model_load", "bk_gbt_model_free",
     "bk_winprob_eval_gbt",
     "bk_mcts_learned_gbt",
+    "bk_heur_plan_size", "bk_rollout_frontier_w", "bk_arena_step_w",
 )
 # bk_debug_mcts_failure record (include/blokus_hip.h BK_DIAG_*)
 DIAG_WORDS = 64
@@ -90,6 +96,42 @@ class BkRolloutCfg(C.Structure):
 class BkSnapPlan(C.Structure):
     """bk_snap_plan: the checkpoint plies of bk_arena_step_snap and the caller's device slots."""
     _fields_ = [("ply_mask", C.c_uint32 * 4), ("states", C.c_void_p), ("sets", C.c_void_p), ("turn", C.c_void_p)]
+
+
+class BkHeurPlan(C.Structure):
+    """bk_heur_plan: the weight sets of bk_rollout_frontier_w / bk_arena_step_w and which set each seat uses."""
+    _fields_ = [("w", (C.c_double * 4) * HEUR_MAX_SETS), ("n_sets", C.c_int32), ("seat_sets_all", C.c_uint8),
+                ("seat_sets", C.c_void_p)]
+
+
+def heur_weight_set(weights) -> tuple:
+    """HeuristicAgent.set_weights(weights) on a fresh agent as (size, corner, edge, centre)
+    floats: the defaults, overridden by the keys given."""
+    weights = weights or {}
+    return tuple(float(weights[k]) if k in weights else d for k, d in zip(HEUR_WEIGHT_KEYS, HEUR_DEFAULT_WEIGHTS))
+
+
+def heur_weight_span(w) -> float:
+    """S of a weight set: the largest |score| its moves can reach (BK_HEUR_MAX_S bounds it)."""
+    return 5.0 * abs(w[0]) + 20.0 * abs(w[1]) + 5.0 * abs(w[2]) + abs(w[3])
+
+
+def heur_set_ok(w) -> bool:
+    """The GPU plays this weight set: finite and S within BK_HEUR_MAX_S."""
+    return all(np.isfinite(x) for x in w) and heur_weight_span(w) <= HEUR_MAX_S
+
+
+def heur_plan(sets, seat_sets_all: int = 0, seat_sets_ptr: int = 0) -> BkHeurPlan:
+    """A bk_heur_plan of `sets` (1..HEUR_MAX_SETS tuples of four weights); seat p of game i
+    uses set (seat_sets[i] >> 2p) & 3, or seat_sets_all's without a per-game array."""
+    plan = BkHeurPlan()
+    plan.n_sets = len(sets)
+    for s, w in enumerate(sets[:HEUR_MAX_SETS]):
+        for k in range(4):
+            plan.w[s][k] = float(w[k])
+    plan.seat_sets_all = int(seat_sets_all) & 0xFF
+    plan.seat_sets = seat_sets_ptr or None
+    return plan
 
 
 SNAP_MAX_PLY = 127  # the highest ply a bk_snap_plan mask can name (a game has at most 84 placements)
@@ -352,6 +394,11 @@ def load():
             "bk_arena_step_snap": (C.c_int, [vp, vp, vp, C.c_int32, P(BkRolloutCfg), vp, vp, vp, vp, vp, vp,
                                              P(BkSnapPlan), C.c_int]),
             "bk_snap_plan_size": (C.c_int, []),
+            "bk_heur_plan_size": (C.c_int, []),
+            "bk_rollout_frontier_w": (C.c_int, [vp, vp, vp, C.c_int32, vp, C.c_int32, P(BkRolloutCfg), vp, vp, vp,
+                                                vp, P(BkHeurPlan), C.c_int]),
+            "bk_arena_step_w": (C.c_int, [vp, vp, vp, C.c_int32, P(BkRolloutCfg), vp, vp, vp, vp, vp, vp,
+                                          P(BkHeurPlan), C.c_int]),
             "bk_mcts_learned": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, P(BkMctsCfg), vp, C.c_int32, vp, vp, vp, vp,
                                           vp, C.c_int32, P(BkWinprobModel), C.c_int32, C.c_double, vp, vp, vp, vp,
                                           vp, vp, C.c_int]),
@@ -690,6 +737,17 @@ class Handle:
                                              C.c_void_p(states_ptr or 0), C.c_void_p(osets_ptr or 0), mem)
         self.check(rc, "bk_rollout_frontier")
 
+    def rollout_frontier_w(self, roots_ptr, sets_ptr, n_roots, index_ptr, n_playouts, cfg: BkRolloutCfg, seeds_ptr,
+                           out_ptr, states_ptr, osets_ptr, plan: BkHeurPlan, mem):
+        """bk_rollout_frontier_w: rollout_frontier whose heuristic seats score with plan's weight sets."""
+        with self._lock:
+            rc = self._L.bk_rollout_frontier_w(self._h, C.c_void_p(roots_ptr), C.c_void_p(sets_ptr), n_roots,
+                                               C.c_void_p(index_ptr or 0), n_playouts, C.byref(cfg),
+                                               C.c_void_p(seeds_ptr or 0), C.c_void_p(out_ptr or 0),
+                                               C.c_void_p(states_ptr or 0), C.c_void_p(osets_ptr or 0),
+                                               C.byref(plan), mem)
+        self.check(rc, "bk_rollout_frontier_w")
+
     def mcts(self, roots_ptr, sets_ptr, players_ptr, hash_ptr, n_games, cfg: BkMctsCfg, zob_ptr, n_zob, zidx_ptr,
              mt_ptr, ttk_ptr, ttv_ptr, ttc_ptr, log_ptr, log_len, nodes_ptr, rewards_ptr, flags_ptr, out_ptr, mem):
         v = lambda x: C.c_void_p(x or 0)  # noqa: E731
@@ -738,6 +796,17 @@ class Handle:
                                        C.c_void_p(masks_ptr), C.c_void_p(quick_ptr), C.c_void_p(forced_ptr),
                                        C.c_void_p(rng_ptr), C.c_void_p(out_ptr), C.c_void_p(stop_ptr), mem)
         self.check(rc, "bk_arena_step")
+
+    def arena_step_w(self, states_ptr, sets_ptr, n, cfg: BkRolloutCfg, masks_ptr, quick_ptr, forced_ptr, rng_ptr,
+                     out_ptr, stop_ptr, plan: BkHeurPlan, mem):
+        """bk_arena_step_w: arena_step whose heuristic seats score with plan's weight sets
+        (quick_ptr, forced_ptr and stop_ptr 0: what bk_arena_advance does)."""
+        with self._lock:
+            rc = self._L.bk_arena_step_w(self._h, C.c_void_p(states_ptr), C.c_void_p(sets_ptr), n, C.byref(cfg),
+                                         C.c_void_p(masks_ptr), C.c_void_p(quick_ptr or 0), C.c_void_p(forced_ptr or 0),
+                                         C.c_void_p(rng_ptr), C.c_void_p(out_ptr), C.c_void_p(stop_ptr or 0),
+                                         C.byref(plan), mem)
+        self.check(rc, "bk_arena_step_w")
 
     def arena_step_snap(self, states_ptr, sets_ptr, n, cfg: BkRolloutCfg, masks_ptr, quick_ptr, forced_ptr, rng_ptr,
                         out_ptr, stop_ptr, plan: BkSnapPlan, mem):

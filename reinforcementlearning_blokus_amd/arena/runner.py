@@ -581,18 +581,60 @@ def _move_tables():
     return _MOVE_TABLES
 
 
+def _heur_weights(config: AgentConfig):
+    """The weight set a heuristic agent's params["weights"] leaves it with (the defaults
+    overridden by the keys given, as HeuristicAgent.set_weights merges), as four floats;
+    None where a value is no number."""
+    from .. import _native as N
+    try:
+        return N.heur_weight_set(config.params.get("weights"))
+    except (TypeError, ValueError):
+        return None
+
+
+def _heur_sets(run_config: RunConfig):
+    """(weight sets, {agent name: its set}) of a run whose heuristic agents have weights of
+    their own -- every heuristic agent of the run gets a set, the default weights' one
+    included (at most four: a run has four agents) -- or None where none has, and the
+    launches are the default-weight ones."""
+    heur = [a for a in run_config.agents if a.type.lower() == "heuristic"]
+    if not any(a.params.get("weights") for a in heur):
+        return None
+    sets: List[Tuple[float, ...]] = []
+    set_of: Dict[str, int] = {}
+    for a in heur:
+        w = _heur_weights(a)
+        if w not in sets:
+            sets.append(w)
+        set_of[a.name] = sets.index(w)
+    return sets, set_of
+
+
+def _seat_sets(seats: Mapping[str, str], set_of: Mapping[str, int]) -> int:
+    """bk_heur_plan.seat_sets byte of one game: bits 2p..2p+1 the set of seat p's agent."""
+    return sum(set_of.get(seats[str(p + 1)], 0) << (2 * p) for p in range(4))
+
+
 def _batchable(run_config: RunConfig, seats: Mapping[str, str]) -> bool:
-    """run_games_batched can play this seating: random / default-weight heuristic seats
-    each with their own agent (a stream per seat), search seats of the supported kinds
-    (FastMCTS kinds only with deterministic_time_budget, the default)."""
+    """run_games_batched can play this seating: random / heuristic seats each with their
+    own agent (a stream per seat), search seats of the supported kinds (FastMCTS kinds only
+    with deterministic_time_budget, the default).  A heuristic agent with weights of its
+    own is batched when the set is finite with S <= BK_HEUR_MAX_S (up to
+    there a certified draw is the reference's) and the run keeps no snapshots (the
+    capturing step kernel has the default weights only)."""
+    from .. import _native as N
     cfgs = {a.name: a for a in run_config.agents}
     names = list(seats.values())
     for name in set(names):
         c = cfgs[name]
         kind = c.type.lower()
         if kind in ("random", "heuristic"):
-            if names.count(name) > 1 or (kind == "heuristic" and c.params.get("weights")):
+            if names.count(name) > 1:
                 return False
+            if kind == "heuristic" and c.params.get("weights"):
+                w = _heur_weights(c)
+                if run_config.snapshots.enabled or w is None or not N.heur_set_ok(w):
+                    return False
         elif kind not in _SEARCH_KINDS:
             return False
         elif kind != "mcts" and not bool(c.params.get("deterministic_time_budget", True)):
@@ -879,6 +921,11 @@ def _run_games_device(run_config: RunConfig, idx: List[int], seats: List[Mapping
     states_d = up(np.repeat(empty_state(), n).view(np.uint8).reshape(n, 256))
     sets_d = up(np.repeat(N.fset_new(1), n).view(np.uint8).reshape(n, -1))  # (every game starts from Board())
     masks_d, quick_d, rng_d = up(masks), up(quick), up(rng.view(np.int32))
+    hsets = _heur_sets(run_config)  # custom heuristic weights: every step is bk_arena_step_w
+    step_kw: Dict[str, Any] = {}
+    if hsets is not None:
+        step_kw = {"heur_sets": hsets[0],
+                   "seat_sets": up(np.array([_seat_sets(seats[i], hsets[1]) for i in range(n)], np.uint8))}
     forced_d = torch.full((n,), -1, dtype=torch.int32, device=dev)
     out_d = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
     stop_d = torch.zeros((n, N.STOP_DTYPE.itemsize), dtype=torch.uint8, device=dev)
@@ -1205,7 +1252,7 @@ def _run_games_device(run_config: RunConfig, idx: List[int], seats: List[Mapping
                 progress(prof["rounds"], int(active.sum()), prof)
             ta = time.perf_counter()
             gpu.arena_step(states_d, sets_d, masks_d, rng_d, quick_d, forced_d, out_d, stop_d,
-                           max_turns=run_config.max_turns, snap=slots)
+                           max_turns=run_config.max_turns, snap=slots, **step_kw)
             # one copy back per step: results, stop infos, the player to move
             step_h = torch.cat([out_d, stop_d, states_d[:, 240:244]], dim=1).cpu().numpy()
             res = np.ascontiguousarray(step_h[:, :32]).view(N.RESULT_DTYPE).reshape(n)
@@ -1578,6 +1625,8 @@ def run_games_batched(run_config: RunConfig, game_indices: Sequence[int], *, run
         agents.append(built)
         per_agent.append({name: {"moves": 0.0, "total_time_ms": 0.0, "total_simulations": 0.0,
                                  "moves_with_simulations": 0.0, "move_times_ms": []} for name in set(st.values())})
+    hsets = _heur_sets(run_config)  # custom heuristic weights: one set byte per game next to its seat mask
+    seat_sets = np.array([_seat_sets(st, hsets[1]) for st in seats], np.uint8) if hsets is not None else None
     results: List[Optional[Dict[str, Any]]] = [None] * n
     active = np.arange(n)
     prof = LAST_BATCH_PROFILE
@@ -1596,7 +1645,8 @@ def run_games_batched(run_config: RunConfig, game_indices: Sequence[int], *, run
         ta = time.perf_counter()
         sub_st, sub_fs, sub_rng = states[active].copy(), sets[active].copy(), rng[active].copy()
         before = sub_st["reserved"].copy()
-        res = gpu.arena_advance(sub_st, sub_fs, masks[active], sub_rng, max_turns=run_config.max_turns)
+        adv_kw = {} if hsets is None else {"heur_sets": hsets[0], "seat_sets": seat_sets[active]}
+        res = gpu.arena_advance(sub_st, sub_fs, masks[active], sub_rng, max_turns=run_config.max_turns, **adv_kw)
         prof["advance_s"] += time.perf_counter() - ta
         states[active], sets[active], rng[active] = sub_st, sub_fs, sub_rng
         stopped = []

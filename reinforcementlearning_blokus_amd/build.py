@@ -45,7 +45,8 @@ def built_hash():
 # then one unit per kernel family, compiled in parallel and linked into one .so
 UNITS = {"host": 1, "movegen": 2, "rollout": 3, "rollout_fr": 4, "rollout_frh": 5, "fastmcts": 6,
          "mcts": 7, "mcts_pair": 8, "mcts_h": 9, "coop": 10, "coop_h": 11, "telemetry": 12,
-         "snapshot": 13, "steplog": 14, "rollout_frhs": 15, "coop_l": 16, "gbt": 17, "coop_g": 18}
+         "snapshot": 13, "steplog": 14, "rollout_frhs": 15, "coop_l": 16, "gbt": 17, "coop_g": 18,
+         "rollout_frhw": 19}
 
 
 # per-unit code-generation flags (measured per kernel).  Machine LICM hoists
@@ -67,7 +68,8 @@ UNIT_FLAGS = {"rollout_fr": _NO_MLICM + _MUX, "rollout": _MUX, "mcts": _MUX, "co
               "coop_l": _NO_MLICM,  # k_mcts_coop_l is k_mcts_coop's tree part: the same reasons
               "coop_g": _NO_MLICM,  # k_mcts_coop_g is k_mcts_coop_l with another value(): coop_l's flags
               "mcts_pair": ("-DBK_STENCIL_COMMON",), "rollout_frh": ("-DBK_STENCIL_PLAIN",),
-              "rollout_frhs": ("-DBK_STENCIL_PLAIN",)}  # k_rollout_fr_h's code plus the capture
+              "rollout_frhs": ("-DBK_STENCIL_PLAIN",),  # k_rollout_fr_h's code plus the capture
+              "rollout_frhw": ("-DBK_STENCIL_PLAIN",)}  # k_rollout_fr_h's code with per-set score tables
 
 
 def compile_library(out: str, defines=(), verbose: bool = True, jobs: int = 0, unit_flags=None) -> str:

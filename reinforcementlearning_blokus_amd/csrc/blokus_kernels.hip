@@ -76,6 +76,7 @@
 #define BK_U_COOP_L 16
 #define BK_U_GBT 17
 #define BK_U_COOP_G 18
+#define BK_U_ROLLOUT_FRHW 19
 #ifndef BK_TU
 #define BK_TU 0
 #endif
@@ -2477,6 +2478,7 @@ __device__ __forceinline__ bool place_frontier_dma(FsLane* fl, int p, int16_t* s
 #define BK_STATUS_UNCERT 16u
 
 struct HeurShared {           // per block (LDS), built at kernel start
+    static constexpr bool kWeighted = false;
     double tk[HK_N];          // exp(K4 / 4)
     double tc[BK_CELLS];      // exp(centre(anchor) / 2)
     int32_t first[BK_PIECES + 1];  // first global orientation of each piece (+ 91)
@@ -2496,11 +2498,66 @@ __device__ void heur_shared_init(HeurShared* hs, int tid, int nthreads) {
     if (tid == 0) hs->first[BK_PIECES] = BK_NUM_ORIENTS;
 }
 
+// Custom weights (k_rollout_fr_hw): the integer K4 exists only for the default weights, so
+// each of up to BK_HEUR_MAX_SETS weight sets w = (size, corner, edge, centre) has tables
+// of its own, e = ta * tcr * tct (the error of the three rounded exponents is
+// what bounds S = 5 |w_size| + 20 |w_corner| + 5 |w_edge| + |w_centre| by BK_HEUR_MAX_S)
+struct HeurSetW {
+    double ta[2][5][6];  // [late][n - 1][edge] exp(w_size n + w_edge (late ? edge / 2 : edge))
+    double tcr[21];      // [corners] exp(w_corner corners)
+    double tct[100];     // [|r - 9.5| - 0.5][|c - 9.5| - 0.5] exp(w_centre centre(anchor))
+};
+struct HeurSharedW {  // per block (LDS), built at kernel start
+    HeurSetW set[BK_HEUR_MAX_SETS];
+    int32_t first[BK_PIECES + 1];  // as HeurShared::first
+};
+struct HeurLaneW {  // what the heur_* routines take as hs: the mover's set (per lane)
+    static constexpr bool kWeighted = true;
+    const HeurSetW* s;
+    const int32_t* first;
+};
+// bk_heur_plan as k_rollout_fr_hw takes it (a kernel argument of its own, as CaptureArgs)
+struct HeurWArgs {
+    double w[BK_HEUR_MAX_SETS][4];
+    int32_t n_sets;
+    uint32_t seat_sets_all;
+    const uint8_t* seat_sets;  // [n_playouts] or nullptr (seat_sets_all)
+};
+
+__device__ void heur_shared_init_w(HeurSharedW* hs, const HeurWArgs& hw, int tid, int nthreads) {
+    constexpr int PER = (int)(sizeof(HeurSetW) / sizeof(double));
+    for (int i = tid; i < BK_HEUR_MAX_SETS * PER; i += nthreads) {
+        const int s = i / PER, j = i - s * PER;
+        // (a set past n_sets is never chosen -- heur_bad_sets refuses the game -- and reads as weights 0)
+        const bool on = s < hw.n_sets;
+        const double w_size = on ? hw.w[s][0] : 0.0, w_corner = on ? hw.w[s][1] : 0.0;
+        const double w_edge = on ? hw.w[s][2] : 0.0, w_centre = on ? hw.w[s][3] : 0.0;
+        double x;
+        if (j < 60) {
+            const int late = j / 30, n = (j % 30) / 6 + 1, edge = j % 6;
+            x = w_size * (double)n + w_edge * (late ? (double)edge * 0.5 : (double)edge);
+        } else if (j < 81) {
+            x = w_corner * (double)(j - 60);
+        } else {
+            const double dr = (double)((j - 81) / 10) + 0.5, dc = (double)((j - 81) % 10) + 0.5;
+            x = w_centre * (1.0 - sqrt(dr * dr + dc * dc) / sqrt(2.0 * (9.5 * 9.5)));
+        }
+        (&hs->set[s].ta[0][0][0])[j] = exp(x);
+    }
+    for (int g = tid; g < BK_NUM_ORIENTS; g += nthreads) {
+        const uint32_t pc = kInfo[g] & 0xFFu;
+        if (g == 0 || (kInfo[g - 1] & 0xFFu) != pc) hs->first[pc - 1] = g;
+    }
+    if (tid == 0) hs->first[BK_PIECES] = BK_NUM_ORIENTS;
+}
+
 // e = exp(score) of orientation (n cells at (cd, cc)) with its box corner at (r, x);
 // rows[R * WAVE].x = the mover's blocked row R before the move (empty and not
-// orthogonally adjacent to the mover = ~B)
+// orthogonally adjacent to the mover = ~B).  hs: the block's default-weight tables, or the
+// lane's weight set (edge_w 3 = late)
+template <typename HS>
 __device__ __forceinline__ double heur_e(int n, const uint32_t (&cd)[5], const uint32_t (&cc)[5], int r, int x,
-                                         const uint2* rows, const HeurShared* hs, int edge_w) {
+                                         const uint2* rows, const HS* hs, int edge_w) {
     int corners = 0, edge = 0;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
@@ -2513,7 +2570,12 @@ __device__ __forceinline__ double heur_e(int n, const uint32_t (&cd)[5], const u
             edge += (R <= 2 || R >= 17 || c <= 2 || c >= 17) ? 1 : 0;
         }
     }
-    return hs->tk[4 * n + 8 * corners - edge_w * edge - HK_MIN] * hs->tc[r * 20 + x];
+    if constexpr (HS::kWeighted) {
+        const int ir = r < 10 ? 9 - r : r - 10, ic = x < 10 ? 9 - x : x - 10;
+        return hs->s->ta[edge_w == 3][n - 1][edge] * hs->s->tcr[corners] * hs->s->tct[ir * 10 + ic];
+    } else {
+        return hs->tk[4 * n + 8 * corners - edge_w * edge - HK_MIN] * hs->tc[r * 20 + x];
+    }
 }
 
 __device__ __forceinline__ void orient_cells(int g, int& n, uint32_t (&cd)[5], uint32_t (&cc)[5]) {
@@ -2528,7 +2590,8 @@ __device__ __forceinline__ void orient_cells(int g, int& n, uint32_t (&cd)[5], u
 
 // sum of e over orientation g's legal anchors (ok rows in rows[r * WAVE].y, r < nr);
 // g is wave-uniform (a stencil-class entry)
-__device__ __forceinline__ double heur_orient_sum(int g, int nr, const uint2* rows, const HeurShared* hs, int edge_w,
+template <typename HS>
+__device__ __forceinline__ double heur_orient_sum(int g, int nr, const uint2* rows, const HS* hs, int edge_w,
                                                   uint32_t& count) {
     int n;
     uint32_t cd[5], cc[5];
@@ -2560,15 +2623,21 @@ __device__ __forceinline__ double heur_orient_sum(int g, int nr, const uint2* ro
     return sum;
 }
 
+// Class entry i of the stencil list that pass A walks.  A plain function only so that the
+// other units' assembly stays what it was: heur_class below became a template over HS, and
+// a unit that does not instantiate it would no longer name kClass in its symbol directives
+__device__ __forceinline__ uint2 heur_class_entry(int i) { return make_uint2(kClass[i][0], kClass[i][1]); }
+
 // pass A over one stencil class: e sums per piece (psum[(piece - 1) * WAVE], doubles in
 // LDS) and the legal-move count, for lanes whose mover plays the heuristic (avail = 0
 // otherwise)
-template <int H, int... T>
+template <typename HS, int H, int... T>
 __device__ __forceinline__ void heur_class(int i0, int i1, const Planes& P, uint32_t avail, uint2* rows,
-                                           double* psum, const HeurShared* hs, int edge_w, uint32_t& count) {
+                                           double* psum, const HS* hs, int edge_w, uint32_t& count) {
 #pragma unroll 1
     for (int i = i0; i < i1; ++i) {
-        const uint32_t w0 = kClass[i][0], w1 = kClass[i][1];
+        const uint2 ce = heur_class_entry(i);
+        const uint32_t w0 = ce.x, w1 = ce.y;
         const uint32_t piece = w0 & 0xFFu;
         const bool av = (avail >> (piece - 1u)) & 1u;
         if (__builtin_amdgcn_ballot_w64(av) == 0ull) continue;
@@ -2582,15 +2651,16 @@ __device__ __forceinline__ void heur_class(int i0, int i1, const Planes& P, uint
     }
 }
 
+template <typename HS>
 __device__ __forceinline__ uint32_t heur_pass_a(const Planes& P, uint32_t avail, uint2* rows, double* psum,
-                                                const HeurShared* hs, int edge_w) {
+                                                const HS* hs, int edge_w) {
 #pragma unroll
     for (int p = 0; p < BK_PIECES; ++p) psum[p * WAVE] = 0.0;
     uint32_t count = 0;
     int tb0 = 0;  // opaque 0 (see movegen_counts)
     asm volatile("" : "+s"(tb0));
     tb0 = __builtin_amdgcn_readfirstlane(tb0);
-#define BK_HEUR_CLASS(i0, i1, H, ...) heur_class<H, __VA_ARGS__>(i0 + tb0, i1 + tb0, P, avail, rows, psum, hs, edge_w, count);
+#define BK_HEUR_CLASS(i0, i1, H, ...) heur_class<HS, H, __VA_ARGS__>(i0 + tb0, i1 + tb0, P, avail, rows, psum, hs, edge_w, count);
     BK_CLASS_LIST(BK_HEUR_CLASS)
 #undef BK_HEUR_CLASS
     return count;
@@ -2603,8 +2673,9 @@ __device__ __forceinline__ void lane_ok_rows(int gs, const uint2* rows, uint32_t
     for (int r = 0; r < 20; ++r) ok[r] = anchor_row(lc, r);
 }
 
+template <typename HS>
 __device__ __forceinline__ double lane_orient_sum(int gs, const uint32_t (&ok)[20], const uint2* rows,
-                                                  const HeurShared* hs, int edge_w) {
+                                                  const HS* hs, int edge_w) {
     int n;
     uint32_t cd[5], cc[5];
     orient_cells(gs, n, cd, cc);
@@ -2626,7 +2697,8 @@ __device__ __forceinline__ double lane_orient_sum(int gs, const uint32_t (&ok)[2
 // crosses it.  rows: {B, C} in LDS.  Returns the orientation (its legal rows in ok) and
 // the cumulative e before it in R; uncertain when the crossing is not where the sums say
 // (rounding: the choice is then not certified).
-__device__ __forceinline__ int heur_pick_orient(const double* psum, const uint2* rows, const HeurShared* hs,
+template <typename HS>
+__device__ __forceinline__ int heur_pick_orient(const double* psum, const uint2* rows, const HS* hs,
                                                 int edge_w, double target, double& R, uint32_t (&ok)[20],
                                                 bool& uncertain) {
     int pstar = -1;
@@ -2672,8 +2744,9 @@ __device__ __forceinline__ int heur_pick_orient(const double* psum, const uint2*
 // Walk orientation gs's anchors in the reference's frontier list order (pass 2 of
 // locate_move_frontier) accumulating e until the cumulative sum passes target.  ok =
 // gs's legal rows; rows[.].y is overwritten, rows[.].x (B) kept.
+template <typename HS>
 __device__ __forceinline__ void heur_walk_frontier(int gs, const uint32_t (&ok)[20], uint2* rows, const int16_t* key,
-                                                   int mask, const HeurShared* hs, int edge_w, double target,
+                                                   int mask, const HS* hs, int edge_w, double target,
                                                    double R, double total, int& out_r, int& out_c,
                                                    bool& uncertain) {
 #pragma unroll
@@ -2728,6 +2801,7 @@ __device__ __forceinline__ void heur_walk_frontier(int gs, const uint32_t (&ok)[
 #define BK_STICKY_GUARD 1u  // a persistent kernel's iteration guard tripped: results incomplete
 #define BK_STICKY_ROOT 2u   // a root_index entry outside [0, n_roots)
 #define BK_STICKY_FASTMCTS 4u  // k_fastmcts: a root with too many children or a short log table
+#define BK_STICKY_HSET 8u   // k_rollout_fr_hw: a heuristic seat names a weight set >= n_sets
 
 struct RolloutArgs {
     const bk_state* roots;
@@ -3387,13 +3461,45 @@ __device__ __forceinline__ void help_report(uint32_t* my, int lane, bool idle, u
     if (!idle) g.status |= my[HELP_FOUND * WAVE + lane] << 8;
 }
 
+// WEIGHTED (k_rollout_fr_hw): game `next` names, for a seat that plays the heuristic, a
+// weight set the plan does not have (a device-path input error: flagged, never played)
+__device__ __forceinline__ bool heur_bad_sets(const RolloutArgs& a, const HeurWArgs& hw, int32_t next) {
+    const uint32_t hm = a.seat_masks ? (a.seat_masks[next] & 0xFu) : (uint32_t)a.cfg.heuristic_seats;
+    const uint32_t ss = hw.seat_sets ? hw.seat_sets[next] : hw.seat_sets_all;
+    bool bad = false;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) bad |= ((hm >> p) & 1u) && (int32_t)((ss >> (2 * p)) & 3u) >= hw.n_sets;
+    if (!bad) return false;
+    atomicOr(&a.counter[2], BK_STICKY_HSET);
+    if (a.out != nullptr) {
+        bk_result r;
+        memset(&r, 0, sizeof r);
+        r.status = (uint8_t)BK_STATUS_BADSET;
+        a.out[next] = r;
+    }
+    return true;
+}
+
+// the hs of the heur_* routines: the block's tables, or the lane's set of HeurSharedW
+__device__ __forceinline__ const HeurShared* heur_ref(const HeurShared* hs, const HeurLaneW&) { return hs; }
+__device__ __forceinline__ const HeurLaneW* heur_ref(const HeurSharedW*, const HeurLaneW& hl) { return &hl; }
+
+template <bool WEIGHTED>
+struct HeurTables { using Shared = HeurShared; };
+template <>
+struct HeurTables<true> { using Shared = HeurSharedW; };
+
 // HELP (k_rollout_fr): idle lanes look ahead for stuck players (BK_SEM_ARENA launches)
-template <bool FR, bool HEUR = false, bool SNAP = false, bool HELP = false>
-__device__ __forceinline__ void rollout_body(const RolloutArgs& a, const CaptureArgs& sn = CaptureArgs{}) {
+// WEIGHTED (k_rollout_fr_hw): heuristic seats score with the weight sets of hw
+template <bool FR, bool HEUR = false, bool SNAP = false, bool HELP = false, bool WEIGHTED = false>
+__device__ __forceinline__ void rollout_body(const RolloutArgs& a, const CaptureArgs& sn = CaptureArgs{},
+                                             const HeurWArgs& hw = HeurWArgs{}) {
     static_assert(!HELP || (FR && !HEUR && !SNAP), "the look-ahead is k_rollout_fr's");
+    static_assert(!WEIGHTED || (FR && HEUR && !SNAP), "weight sets are k_rollout_fr_hw's");
+    using HeurTab = typename HeurTables<WEIGHTED>::Shared;
     constexpr int BLK = HEUR ? HBLOCK : BLOCK;
     constexpr int AREA = HEUR ? HEUR_WORDS : FR ? ROLL_WORDS_FR : ROLL_WORDS_PER_WAVE;
-    constexpr int HS_WORDS = HEUR ? (int)(sizeof(HeurShared) + 7) / 4 : 0;
+    constexpr int HS_WORDS = HEUR ? (int)(sizeof(HeurTab) + 7) / 4 : 0;
     // HEUR (k_rollout_fr_h): + the CPython cell hashes (shared by the block) for the
     // frontier tables and the policy's exp tables; k_rollout_fr reads the hashes from
     // global memory through the L1, so its LDS fits 4 blocks per CU
@@ -3402,11 +3508,12 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Capture
     const int lane0 = threadIdx.x & (WAVE - 1), wv = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
     uint64_t* htab_lds = reinterpret_cast<uint64_t*>(lds + AREA * (BLK / WAVE));
     const uint64_t* htab = HT_LDS ? htab_lds : kCellHash;
-    HeurShared* hs = reinterpret_cast<HeurShared*>(lds + AREA * (BLK / WAVE) + (HT_LDS ? 2 * BK_CELLS : 0));
+    HeurTab* hs = reinterpret_cast<HeurTab*>(lds + AREA * (BLK / WAVE) + (HT_LDS ? 2 * BK_CELLS : 0));
     if constexpr (HT_LDS) {
         for (int i = threadIdx.x; i < BK_CELLS; i += BLK) htab_lds[i] = kCellHash[i];
     }
-    if constexpr (HEUR) heur_shared_init(hs, threadIdx.x, BLK);
+    if constexpr (WEIGHTED) heur_shared_init_w(hs, hw, threadIdx.x, BLK);
+    else if constexpr (HEUR) heur_shared_init(hs, threadIdx.x, BLK);
     if constexpr (HT_LDS || HEUR) __syncthreads();
     const uint32_t slot0 = blockIdx.x * BLK + threadIdx.x;
     // The lane's slot and lane index are laundered once per ply, so the addresses derived
@@ -3452,6 +3559,9 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Capture
                 if (next >= a.n_playouts) { done = true; break; }
                 // bk_arena_step: a game whose search is still running is left untouched
                 if (HEUR && a.forced && a.forced[next] == BK_FORCE_SKIP) continue;
+                if constexpr (WEIGHTED) {
+                    if (heur_bad_sets(a, hw, next)) continue;
+                }
                 if constexpr (FR && !HEUR)
                     start_game<true, true>(a, g, slab, slot, next, htab, live_masks(slab, &a.fslab[slot], lm_in_slab));
                 else
@@ -3524,6 +3634,13 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Capture
         double h_target = 0.0, h_R = 0.0, h_total = 0.0;
         uint32_t h_ok[20];
         bool h_unc = false;
+        // what the heur_* routines score with: the block's tables, or (WEIGHTED) the tables
+        // of the set that the game's seat-to-set map gives the seat to move -- per lane
+        HeurLaneW hl{};
+        if constexpr (WEIGHTED) {
+            const uint32_t ss = !heur ? 0u : hw.seat_sets ? hw.seat_sets[g.pid] : hw.seat_sets_all;
+            hl = HeurLaneW{&hs->set[(ss >> (2 * p)) & 3u], hs->first};
+        }
         if constexpr (HEUR) {
             total = 0;
             // uniform-random movers: counts, draw, orientation (before the area is reused)
@@ -3546,7 +3663,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Capture
                 const int edge_w = (g.move_count0 + g.plies) < 30 ? 6 : 3;  // move_count / 100.0 < 0.3
 #pragma unroll
                 for (int R = 0; R < 20; ++R) rows_lds[R * WAVE].x = P.b(R);
-                const uint32_t t = heur_pass_a(P, heur ? avail : 0u, rows_lds, psum, hs, edge_w);
+                const uint32_t t = heur_pass_a(P, heur ? avail : 0u, rows_lds, psum, heur_ref(hs, hl), edge_w);
 #pragma unroll
                 for (int R = 0; R < 20; ++R) rows_lds[R * WAVE] = make_uint2(P.b(R), P.c(R));
                 if (heur) {
@@ -3555,7 +3672,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Capture
 #pragma unroll 1
                         for (int q = 0; q < BK_PIECES; ++q) h_total += psum[q * WAVE];
                         h_target = draw_double(a, g, slab) * h_total;
-                        gs = heur_pick_orient(psum, rows_lds, hs, edge_w, h_target, h_R, h_ok, h_unc);
+                        gs = heur_pick_orient(psum, rows_lds, heur_ref(hs, hl), edge_w, h_target, h_R, h_ok, h_unc);
                     }
                 }
             }
@@ -3629,7 +3746,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs& a, const Capture
                 ac = 0;
             } else if (heur) {
                 const int edge_w = (g.move_count0 + g.plies) < 30 ? 6 : 3;
-                heur_walk_frontier(gs, h_ok, rows_lds, fs->key[p], fmask, hs, edge_w, h_target, h_R, h_total,
+                heur_walk_frontier(gs, h_ok, rows_lds, fs->key[p], fmask, heur_ref(hs, hl), edge_w, h_target, h_R, h_total,
                                    ar, ac, h_unc);
                 if (h_unc) g.status |= BK_STATUS_UNCERT;
             } else {
@@ -3760,6 +3877,14 @@ __global__ __launch_bounds__(HBLOCK, 2) void k_rollout_fr_hs(RolloutArgs a, Capt
 }
 #else
 __global__ void k_rollout_fr_hs(RolloutArgs a, CaptureArgs sn);
+#endif
+// k_rollout_fr_h whose heuristic seats score with custom weight sets (bk_*_w)
+#if BK_DEF(BK_U_ROLLOUT_FRHW)
+__global__ __launch_bounds__(HBLOCK, 2) void k_rollout_fr_hw(RolloutArgs a, HeurWArgs hw) {
+    rollout_body<true, true, false, false, true>(a, CaptureArgs{}, hw);
+}
+#else
+__global__ void k_rollout_fr_hw(RolloutArgs a, HeurWArgs hw);
 #endif
 
 // ------------------------------------------------------------------------------------
@@ -7818,6 +7943,9 @@ int bk_synchronize(bk_handle h) {
         if (sticky & BK_STICKY_FASTMCTS)
             return set_err(h, BK_EINVAL, "device-path bk_fastmcts: a root with more than BK_FASTMCTS_MAX_CHILDREN "
                                          "children or iterations past the log table (its output is not set)%s", "");
+        if (sticky & BK_STICKY_HSET)
+            return set_err(h, BK_EINVAL, "device-path launch: a heuristic seat names a weight set >= n_sets "
+                                         "(status BK_STATUS_BADSET, game not played)%s", "");
         return set_err(h, BK_EINVAL, "device-path launch: root_index entry outside [0, n_roots)%s", "");
     }
     return BK_OK;
@@ -8023,13 +8151,30 @@ int bk_has_moves(bk_handle h, const bk_state* states, int32_t n, uint8_t* out_ma
     return st.finish();
 }
 
+// a bk_heur_plan's own rules (NULL: no plan)
+static int check_heur_plan(bk_handle h, const bk_heur_plan* plan) {
+    if (!plan) return BK_OK;
+    if (plan->n_sets < 1 || plan->n_sets > BK_HEUR_MAX_SETS)
+        return set_err(h, BK_EINVAL, "bk_heur_plan: n_sets outside 1..BK_HEUR_MAX_SETS%s", "");
+    for (int s = 0; s < plan->n_sets; ++s) {
+        const double* w = plan->w[s];
+        for (int k = 0; k < 4; ++k)
+            if (!isfinite(w[k])) return set_err(h, BK_EINVAL, "bk_heur_plan: a weight is not finite%s", "");
+        if (5.0 * fabs(w[0]) + 20.0 * fabs(w[1]) + 5.0 * fabs(w[2]) + fabs(w[3]) > BK_HEUR_MAX_S)
+            return set_err(h, BK_EINVAL, "bk_heur_plan: a set's S = 5|size| + 20|corner| + 5|edge| + |centre| exceeds "
+                                         "BK_HEUR_MAX_S%s", "");
+    }
+    return BK_OK;
+}
+
 static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, const int32_t* root_index,
                            int32_t n_playouts, const bk_rollout_cfg* cfg, const uint32_t* compat_seeds,
                            bk_result* out, bk_state* out_states, int mem, const bk_fset* root_sets = nullptr,
                            bk_fset* out_sets = nullptr, const uint8_t* seat_masks = nullptr,
                            uint32_t* rng_io = nullptr, const uint8_t* quick_masks = nullptr,
                            const int32_t* forced = nullptr, bk_stop_info* stop_out = nullptr,
-                           const bk_snap_plan* plan = nullptr) {
+                           const bk_snap_plan* plan = nullptr, const bk_heur_plan* hplan = nullptr) {
+    // (hplan: checked by its two callers, check_heur_plan)
     if (!h || !roots || !cfg || n_roots <= 0 || n_playouts < 0 || (mem != BK_MEM_HOST && mem != BK_MEM_DEVICE))
         return set_err(h, BK_EINVAL, "bk_rollout: invalid arguments%s", "");
     if (cfg->semantics != BK_SEM_ARENA && cfg->semantics != BK_SEM_ROLLOUT && cfg->semantics != BK_SEM_ADVANCE)
@@ -8058,6 +8203,14 @@ static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, 
         for (int32_t i = 0; i < n_playouts; ++i)
             if (root_index[i] < 0 || root_index[i] >= n_roots)
                 return set_err(h, BK_EINVAL, "bk_rollout: root_index entry outside [0, n_roots)%s", "");
+    if (hplan && mem == BK_MEM_HOST)  // (device memory: the kernel flags such a game, BK_STATUS_BADSET)
+        for (int32_t i = 0; i < n_playouts; ++i) {
+            const uint32_t hm = seat_masks ? (seat_masks[i] & 0xFu) : (uint32_t)cfg->heuristic_seats;
+            const uint32_t ss = hplan->seat_sets ? hplan->seat_sets[i] : hplan->seat_sets_all;
+            for (int p = 0; p < 4; ++p)
+                if (((hm >> p) & 1u) && (int32_t)((ss >> (2 * p)) & 3u) >= hplan->n_sets)
+                    return set_err(h, BK_EINVAL, "bk_heur_plan: a heuristic seat names a weight set >= n_sets%s", "");
+        }
     const size_t np = (size_t)n_playouts;
     Staging st(h, mem);
     const auto s_roots = st.in(roots, sizeof(bk_state) * (size_t)n_roots);
@@ -8069,6 +8222,7 @@ static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, 
     const auto s_rng = st.inout(rng_io, sizeof(uint32_t) * 16 * np);
     const auto s_quick = st.in(quick_masks, np);
     const auto s_forced = st.in(forced, sizeof(int32_t) * np);
+    const auto s_hsets = st.in(hplan ? hplan->seat_sets : nullptr, np);
     const auto s_stop = st.out(stop_out, sizeof(bk_stop_info) * np);
     // in host memory the outputs are copies of their own, also where the caller advances
     // states and sets in place (bk_arena_advance / bk_arena_step)
@@ -8126,6 +8280,13 @@ static int launch_playouts(bk_handle h, const bk_state* roots, int32_t n_roots, 
                        plan->states, plan->sets, plan->turn};
         for (int w = 0; w < 4; ++w) sn.k += (uint32_t)__builtin_popcount(sn.ply_mask[w]);
         BK_LAUNCH(h, k_rollout_fr_hs, dim3(blocks), dim3(HBLOCK), a, sn);
+    } else if (heur && hplan) {  // bk_rollout_frontier_w / bk_arena_step_w
+        HeurWArgs hw;
+        memcpy(hw.w, hplan->w, sizeof hw.w);
+        hw.n_sets = hplan->n_sets;
+        hw.seat_sets_all = hplan->seat_sets_all;
+        hw.seat_sets = s_hsets.dev();
+        BK_LAUNCH(h, k_rollout_fr_hw, dim3(blocks), dim3(HBLOCK), a, hw);
     } else if (heur) BK_LAUNCH(h, k_rollout_fr_h, dim3(blocks), dim3(HBLOCK), a);
     else if (fr) BK_LAUNCH(h, k_rollout_fr, dim3(blocks), dim3(BLOCK), a);
     else if (cfg->semantics == BK_SEM_ADVANCE) BK_LAUNCH(h, k_advance, dim3(blocks), dim3(BLOCK), a);
@@ -8535,6 +8696,15 @@ static int check_arena_call(bk_handle h, const char* name, const bk_state* state
     return BK_OK;
 }
 
+// bk_arena_step / bk_arena_step_w: host-memory forced moves are checked before the launch
+static int check_forced(bk_handle h, const char* name, const int32_t* forced, int32_t n, int mem) {
+    if (mem == BK_MEM_HOST && forced)
+        for (int32_t i = 0; i < n; ++i)
+            if (forced[i] < BK_FORCE_SKIP || (forced[i] >= 0 && !(forced[i] & BK_FORCE_INDEX) && forced[i] >= BK_NUM_ORIENTS * 400))
+                return set_err(h, BK_EINVAL, "%s: forced move out of range", name);
+    return BK_OK;
+}
+
 int bk_arena_advance(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const bk_rollout_cfg* cfg,
                      const uint8_t* seat_masks, uint32_t* rng_state, bk_result* out, int mem) {
     if (int rc = check_arena_call(h, "bk_arena_advance", states, sets, n, cfg, seat_masks, rng_state, out, mem)) return rc;
@@ -8549,16 +8719,30 @@ int bk_arena_step(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const
     if (int rc = check_arena_call(h, "bk_arena_step", states, sets, n, cfg, seat_masks, rng_state, out, mem)) return rc;
     if (quick_masks && !stop_out)
         return set_err(h, BK_EINVAL, "bk_arena_step: quick_masks goes with stop_out%s", "");
-    if (mem == BK_MEM_HOST && forced)
-        for (int32_t i = 0; i < n; ++i)
-            if (forced[i] < BK_FORCE_SKIP || (forced[i] >= 0 && !(forced[i] & BK_FORCE_INDEX) && forced[i] >= BK_NUM_ORIENTS * 400))
-                return set_err(h, BK_EINVAL, "bk_arena_step: forced move out of range%s", "");
+    if (int rc = check_forced(h, "bk_arena_step", forced, n, mem)) return rc;
     if (n == 0) return BK_OK;
     return launch_playouts(h, states, n, nullptr, n, cfg, nullptr, out, states, mem, sets, sets, seat_masks,
                            rng_state, quick_masks, forced, stop_out);
 }
 
 int bk_snap_plan_size(void) { return (int)sizeof(bk_snap_plan); }
+
+int bk_heur_plan_size(void) { return (int)sizeof(bk_heur_plan); }
+
+int bk_arena_step_w(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const bk_rollout_cfg* cfg,
+                    const uint8_t* seat_masks, const uint8_t* quick_masks, const int32_t* forced, uint32_t* rng_state,
+                    bk_result* out, bk_stop_info* stop_out, const bk_heur_plan* plan, int mem) {
+    if (!plan)
+        return bk_arena_step(h, states, sets, n, cfg, seat_masks, quick_masks, forced, rng_state, out, stop_out, mem);
+    if (int rc = check_arena_call(h, "bk_arena_step_w", states, sets, n, cfg, seat_masks, rng_state, out, mem)) return rc;
+    if (quick_masks && !stop_out)
+        return set_err(h, BK_EINVAL, "bk_arena_step_w: quick_masks goes with stop_out%s", "");
+    if (int rc = check_forced(h, "bk_arena_step_w", forced, n, mem)) return rc;
+    if (int rc = check_heur_plan(h, plan)) return rc;
+    if (n == 0) return BK_OK;
+    return launch_playouts(h, states, n, nullptr, n, cfg, nullptr, out, states, mem, sets, sets, seat_masks,
+                           rng_state, quick_masks, forced, stop_out, nullptr, plan);
+}
 
 int bk_arena_step_snap(bk_handle h, bk_state* states, bk_fset* sets, int32_t n, const bk_rollout_cfg* cfg,
                        const uint8_t* seat_masks, const uint8_t* quick_masks, const int32_t* forced,
@@ -8594,6 +8778,24 @@ int bk_rollout_frontier(bk_handle h, const bk_state* roots, const bk_fset* root_
         return set_err(h, BK_EINVAL, "bk_rollout_frontier: out is NULL%s", "");
     return launch_playouts(h, roots, n_roots, root_index, n_playouts, cfg, compat_seeds, out, out_states, mem,
                            root_sets, out_sets);
+}
+
+int bk_rollout_frontier_w(bk_handle h, const bk_state* roots, const bk_fset* root_sets, int32_t n_roots,
+                          const int32_t* root_index, int32_t n_playouts, const bk_rollout_cfg* cfg,
+                          const uint32_t* compat_seeds, bk_result* out, bk_state* out_states, bk_fset* out_sets,
+                          const bk_heur_plan* plan, int mem) {
+    if (!plan)
+        return bk_rollout_frontier(h, roots, root_sets, n_roots, root_index, n_playouts, cfg, compat_seeds, out,
+                                   out_states, out_sets, mem);
+    if (!cfg || cfg->order != BK_ORDER_FRONTIER || !root_sets)
+        return set_err(h, BK_EINVAL, "bk_rollout_frontier_w: needs BK_ORDER_FRONTIER and root_sets%s", "");
+    if ((cfg->semantics == BK_SEM_ADVANCE && !out_states) || (cfg->semantics == BK_SEM_ROLLOUT && out_states))
+        return set_err(h, BK_EINVAL, "bk_rollout_frontier_w: out_states goes with BK_SEM_ADVANCE / BK_SEM_ARENA%s", "");
+    if (cfg->semantics != BK_SEM_ADVANCE && !out)
+        return set_err(h, BK_EINVAL, "bk_rollout_frontier_w: out is NULL%s", "");
+    if (int rc = check_heur_plan(h, plan)) return rc;
+    return launch_playouts(h, roots, n_roots, root_index, n_playouts, cfg, compat_seeds, out, out_states, mem,
+                           root_sets, out_sets, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, plan);
 }
 
 // ---- host-side frontier tables (no GPU) ---------------------------------------------

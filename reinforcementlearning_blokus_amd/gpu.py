@@ -399,17 +399,35 @@ class BlokusGPU:
                          rng: int = N.RNG_NUMPY_MT, seed: int = 0, max_plies: int | None = None,
                          compat_seeds=None, root_index=None, seats_share_stream: bool = False, out=None,
                          with_results: bool = False, with_states: bool = False, heuristic_seats: int = 0,
-                         stream_base: int = 0):
+                         stream_base: int = 0, heur_sets=None, seat_sets=None):
         """Playouts in the reference's FRONTIER list order (bk_rollout_frontier): with the
         numpy-MT compat stream these are the reference's default-config games.
         root_sets: FSET_DTYPE records (one per root).  Host numpy in/out.  SEM_ADVANCE
         returns (states, tables[, results]); SEM_ARENA with with_states returns
         (states, tables, results): the final positions as well.  heuristic_seats: bit p =
-        seat p plays HeuristicAgent (its draws from the seat's compat stream)."""
+        seat p plays HeuristicAgent (its draws from the seat's compat stream).
+        heur_sets (1..4 tuples of the four HeuristicAgent weights): bk_rollout_frontier_w --
+        heuristic seat p of playout i scores with set (seat_sets[i] >> 2p) & 3; seat_sets a
+        uint8 array / tensor of n_playouts, or one int for every playout."""
         if max_plies is None:
             max_plies = 2500 if semantics == N.SEM_ARENA else 50
         cfg = N.BkRolloutCfg(semantics, N.ORDER_FRONTIER, rng, max_plies, seed & (2**64 - 1),
                              int(seats_share_stream), int(heuristic_seats), _stream_base(stream_base, n_playouts))
+        plan = None
+        if heur_sets is not None:
+            if seat_sets is None or isinstance(seat_sets, (int, np.integer)):
+                plan = N.heur_plan(heur_sets, int(seat_sets or 0))
+            elif _is_torch(seat_sets) != _is_torch(roots):
+                raise ValueError("rollout_frontier: seat_sets lives where roots live (host array or device tensor)")
+            elif _is_torch(seat_sets):
+                import torch
+                _check_device_tensor(seat_sets, "seat_sets", torch.uint8, (n_playouts,), self.device)
+                plan = N.heur_plan(heur_sets, 0, seat_sets.data_ptr())
+            else:
+                seat_sets = np.ascontiguousarray(seat_sets, dtype=np.uint8)  # (kept alive to the end of the call)
+                if seat_sets.shape != (n_playouts,):
+                    raise ValueError(f"rollout_frontier: seat_sets {seat_sets.shape}, expected ({n_playouts},)")
+                plan = N.heur_plan(heur_sets, 0, seat_sets.ctypes.data)
         if _is_torch(roots):  # device tensors: roots uint8 [n,256], root_sets uint8 [n,2080]
             import torch
             assert semantics != N.SEM_ADVANCE, "device path: playout results only"
@@ -419,10 +437,10 @@ class BlokusGPU:
             _check_device_tensor(root_sets, "root_sets", torch.uint8, (roots.shape[0], N.FSET_DTYPE.itemsize),
                                  self.device)
             self._stream_from_torch()
-            self.handle.rollout_frontier(roots.data_ptr(), root_sets.data_ptr(), roots.shape[0],
-                                         root_index.data_ptr() if root_index is not None else 0, n_playouts, cfg,
-                                         compat_seeds.data_ptr() if compat_seeds is not None else 0,
-                                         out.data_ptr(), 0, 0, N.MEM_DEVICE)
+            self._frontier_launch(plan, roots.data_ptr(), root_sets.data_ptr(), roots.shape[0],
+                                  root_index.data_ptr() if root_index is not None else 0, n_playouts, cfg,
+                                  compat_seeds.data_ptr() if compat_seeds is not None else 0,
+                                  out.data_ptr(), 0, 0, N.MEM_DEVICE)
             return out
         st = np.ascontiguousarray(roots).view(np.uint8).reshape(-1, 256)
         fs = np.ascontiguousarray(root_sets, dtype=N.FSET_DTYPE)
@@ -437,24 +455,34 @@ class BlokusGPU:
             out_st = np.zeros(n_playouts, dtype=STATE_DTYPE)
             out_fs = np.zeros(n_playouts, dtype=N.FSET_DTYPE)
             res = np.zeros(n_playouts, dtype=RESULT_DTYPE) if with_results else None
-            self.handle.rollout_frontier(st.ctypes.data, fs.ctypes.data, st.shape[0],
-                                         idx.ctypes.data if idx is not None else 0, n_playouts, cfg,
-                                         seeds.ctypes.data if seeds is not None else 0,
-                                         res.ctypes.data if res is not None else 0, out_st.ctypes.data,
-                                         out_fs.ctypes.data, N.MEM_HOST)
+            self._frontier_launch(plan, st.ctypes.data, fs.ctypes.data, st.shape[0],
+                                  idx.ctypes.data if idx is not None else 0, n_playouts, cfg,
+                                  seeds.ctypes.data if seeds is not None else 0,
+                                  res.ctypes.data if res is not None else 0, out_st.ctypes.data,
+                                  out_fs.ctypes.data, N.MEM_HOST)
             return (out_st, out_fs, res) if with_results else (out_st, out_fs)
         res = np.zeros(n_playouts, dtype=RESULT_DTYPE)
-        self.handle.rollout_frontier(st.ctypes.data, fs.ctypes.data, st.shape[0],
-                                     idx.ctypes.data if idx is not None else 0, n_playouts, cfg,
-                                     seeds.ctypes.data if seeds is not None else 0, res.ctypes.data, 0, 0,
-                                     N.MEM_HOST)
+        self._frontier_launch(plan, st.ctypes.data, fs.ctypes.data, st.shape[0],
+                              idx.ctypes.data if idx is not None else 0, n_playouts, cfg,
+                              seeds.ctypes.data if seeds is not None else 0, res.ctypes.data, 0, 0, N.MEM_HOST)
         return res
 
+    def _frontier_launch(self, plan, *args):
+        """bk_rollout_frontier(*args), or with a weight-set plan bk_rollout_frontier_w (the
+        plan goes before the last argument, mem)."""
+        if plan is None:
+            self.handle.rollout_frontier(*args)
+        else:
+            self.handle.rollout_frontier_w(*args[:-1], plan, args[-1])
+
     # ------------------------------------------------------------------ arena with search seats
-    def arena_advance(self, states, sets, seat_masks, rng_state, *, max_turns: int = 2500):
+    def arena_advance(self, states, sets, seat_masks, rng_state, *, max_turns: int = 2500, heur_sets=None,
+                      seat_sets=None):
         """bk_arena_advance on host arrays, in place: states (STATE_DTYPE[n]), sets
         (FSET_DTYPE[n]), rng_state uint32[n, 16]; seat_masks uint8[n] (bits 0-3 heuristic
-        seats, 4-7 stop seats).  Returns RESULT_DTYPE[n]."""
+        seats, 4-7 stop seats).  Returns RESULT_DTYPE[n].  heur_sets / seat_sets (uint8[n]):
+        the heuristic seats' weight sets, as rollout_frontier takes them -- the same advance
+        through bk_arena_step_w (no forced moves, no stop infos)."""
         n = len(states)
         assert states.dtype == STATE_DTYPE and sets.dtype == N.FSET_DTYPE and len(sets) == n
         assert states.flags.c_contiguous and sets.flags.c_contiguous
@@ -466,21 +494,34 @@ class BlokusGPU:
         if n == 0:
             return out
         self.handle.set_stream(None)
+        if heur_sets is not None:
+            seat_sets = np.ascontiguousarray(seat_sets, dtype=np.uint8)
+            assert seat_sets.shape == (n,)
+            self.handle.arena_step_w(states.ctypes.data, sets.ctypes.data, n, cfg, masks.ctypes.data, 0, 0,
+                                     rng_state.ctypes.data, out.ctypes.data, 0,
+                                     N.heur_plan(heur_sets, 0, seat_sets.ctypes.data), N.MEM_HOST)
+            return out
         self.handle.arena_advance(states.ctypes.data, sets.ctypes.data, n, cfg, masks.ctypes.data,
                                   rng_state.ctypes.data, out.ctypes.data, N.MEM_HOST)
         return out
 
     def arena_step(self, states, sets, seat_masks, rng_state, quick_masks, forced, out, stop_out, *,
-                   max_turns: int = 2500, snap: "SnapSlots | None" = None):
+                   max_turns: int = 2500, snap: "SnapSlots | None" = None, heur_sets=None, seat_sets=None):
         """bk_arena_step on device tensors, in place (BK_MEM_DEVICE, torch's current
         stream): states uint8[n,256], sets uint8[n,2080], seat_masks / quick_masks uint8[n],
         forced int32[n], rng_state int32[n,16], out uint8[n,32], stop_out uint8[n,16]
         (STOP_DTYPE).  No position or table crosses PCIe (config 4's device driver).
         snap (SnapSlots): bk_arena_step_snap instead -- the same step, and every placement
         that reaches one of snap.plies leaves its position, tables and turn count in the
-        game's slot for that ply (k_rollout_fr_hs)."""
+        game's slot for that ply (k_rollout_fr_hs).
+        heur_sets / seat_sets (uint8[n] on the device): bk_arena_step_w instead -- the
+        heuristic seats score with their weight sets (k_rollout_fr_hw; not with snap)."""
         import torch
         n = states.shape[0]
+        if heur_sets is not None:
+            if snap is not None:
+                raise ValueError("arena_step: no checkpoint capture with custom heuristic weights")
+            _check_device_tensor(seat_sets, "seat_sets", torch.uint8, (n,), self.device)
         if snap is not None:
             k = len(snap.plies)
             if k == 0 or snap.plies != N.snap_plan_plies(snap.plies):
@@ -509,6 +550,12 @@ class BlokusGPU:
             self.handle.arena_step_snap(states.data_ptr(), sets.data_ptr(), n, cfg, seat_masks.data_ptr(),
                                         quick_masks.data_ptr(), forced.data_ptr(), rng_state.data_ptr(),
                                         out.data_ptr(), stop_out.data_ptr(), plan, N.MEM_DEVICE)
+            return
+        if heur_sets is not None:
+            self.handle.arena_step_w(states.data_ptr(), sets.data_ptr(), n, cfg, seat_masks.data_ptr(),
+                                     quick_masks.data_ptr(), forced.data_ptr(), rng_state.data_ptr(), out.data_ptr(),
+                                     stop_out.data_ptr(), N.heur_plan(heur_sets, 0, seat_sets.data_ptr()),
+                                     N.MEM_DEVICE)
             return
         self.handle.arena_step(states.data_ptr(), sets.data_ptr(), n, cfg, seat_masks.data_ptr(),
                                quick_masks.data_ptr(), forced.data_ptr(), rng_state.data_ptr(), out.data_ptr(),
