@@ -448,15 +448,20 @@ def _orients():
     return _ORIENTS
 
 
-def heuristic_score(b, player, move):
-    """_evaluate_move of move = g * 400 + anchor for player (0..3) on oracle board b."""
+HEUR_DEFAULT_WEIGHTS = (1.0, 2.0, -1.5, 0.5)  # piece_size, corner_creation, edge_avoidance, center_preference
+
+
+def heuristic_score(b, player, move, weights=None):
+    """_evaluate_move of move = g * 400 + anchor for player (0..3) on oracle board b;
+    weights = (size, corner, edge, centre) after set_weights (:147-155), else the defaults."""
+    w_size, w_corner, w_edge, w_centre = HEUR_DEFAULT_WEIGHTS if weights is None else weights
     grid = b.grid
     g, a = divmod(int(move), 400)
     ar, ac = divmod(a, 20)
     cells = [(ar + dr, ac + dc) for dr, dc in _orients()[g][2]]
     pv = player + 1
     score = 0.0
-    score += 1.0 * len(cells)
+    score += w_size * len(cells)
     corners = 0
     for r, c in cells:
         for dr, dc in ((-1, -1), (-1, 1), (1, -1), (1, 1)):
@@ -471,33 +476,35 @@ def heuristic_score(b, player, move):
                     break
             if safe:
                 corners += 1
-    score += 2.0 * corners
+    score += w_corner * corners
     edge = sum(1 for r, c in cells if min(r, c, 19 - r, 19 - c) <= 2)
     edge_score = edge if b.move_count / 100.0 < 0.3 else edge * 0.5
-    score += -1.5 * edge_score
+    score += w_edge * edge_score
     distance = np.sqrt((ar - 9.5) ** 2 + (ac - 9.5) ** 2)
     center = 1.0 - distance / np.sqrt(2 * (9.5 ** 2))
-    score += 0.5 * center
+    score += w_centre * center
     return score
 
 
-def heuristic_choice(b, player, rng):
+def heuristic_choice(b, player, rng, weights=None):
     """HeuristicAgent.select_action on b for player with numpy RandomState rng: the chosen
-    move int, or None with no legal move (no draw then)."""
+    move int, or None with no legal move (no draw then).  weights: as heuristic_score."""
     moves = legal_moves(b, player, ORDER_FRONTIER)
     if not moves:
         return None
-    x = np.array([heuristic_score(b, player, m) for m in moves]) / 1.0
+    x = np.array([heuristic_score(b, player, m, weights) for m in moves]) / 1.0
     e = np.exp(x - np.max(x))
     p = e / np.sum(e)
     return moves[rng.choice(len(moves), p=p)]
 
 
-def mixed_playout_arena(b, seeds, heuristic_seats, max_turns=2500):
+def mixed_playout_arena(b, seeds, heuristic_seats, max_turns=2500, weights=None):
     """Arena game loop (arena_runner.py:652-697, pass when stuck, terminal when nobody can
     move) from b with one agent per seat: HeuristicAgent(seeds[p]) where bit p of
     heuristic_seats is set, else RandomAgent(seeds[p]) (randint over the frontier-order
-    list).  Returns (scores, winner_mask, moves, passes, turns, trace)."""
+    list).  weights: one (size, corner, edge, centre) for every heuristic seat, or a list of
+    four, one per seat.  Returns (scores, winner_mask, moves, passes, turns, trace)."""
+    per_seat = [weights] * 4 if weights is None or not hasattr(weights[0], "__len__") else list(weights)
     rngs = [np.random.RandomState(int(s)) for s in seeds]
     passes = turns = 0
     trace = []
@@ -507,7 +514,7 @@ def mixed_playout_arena(b, seeds, heuristic_seats, max_turns=2500):
         p = b.cur
         turns += 1
         if (heuristic_seats >> p) & 1:
-            mv = heuristic_choice(b, p, rngs[p])
+            mv = heuristic_choice(b, p, rngs[p], per_seat[p])
         else:
             lm = legal_moves(b, p, ORDER_FRONTIER)
             mv = lm[rngs[p].randint(0, len(lm))] if lm else None
